@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: ray-samples/sec of the K-Planes training step on synthetic Lego-shaped input.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+W untimed warm-up steps, then exactly K timed steps (--windows M > 1 adds M - 1 variance windows of K steps each).  The inputs
+are seeded: the same arguments give the same inputs on every run.  --dump-outputs DIR writes what the last timed step computed
+(loss, batch counts, parameters, occupancy grid: dump_outputs) as DIR/<name>.npy, so that two builds can be compared output for
+output.
 
 Workload (BASELINE.json configs[2], the configuration the metric is quoted on):
 K-Planes field (3 scales x 3 planes of 32 channels, 128^2/256^2/512^2) + Vanilla sigma / colour
@@ -142,6 +147,16 @@ def bench_grid0(decay: float, res: int = 128):
     return torch.where(xx * xx + yy * yy + zz * zz < 0.25, 1.0, decay ** 20).to(torch.float32)
 
 
+def replay_step(train_step: int):
+    """the step psnr_replay walks to after a timed run that ended on `train_step`: the smallest step of tests/golden/G21_psnr_bench.json
+    at or after it (the replay trainer is not the timed one, so it can go on to where the golden has an entry); None beyond the golden"""
+    try:
+        gold = json.load(open(os.path.join(ROOT, "tests", "golden", "G21_psnr_bench.json")))
+    except Exception:       # noqa: BLE001
+        return None
+    return min((int(s) for s in gold["runs"][0]["psnr"] if int(s) >= train_step), default=None)
+
+
 def psnr_replay(o, d, rgbs, dev, n_steps: int, grid0, ho, hd, hrgb):
     """PSNR@step against the reference recipe ON THE CONFIGURATION THE METRIC IS QUOTED ON (BASELINE.json; run.py:53-54,97-319): a second
     trainer with the harness' replayable random streams (TrainConfig.host_shuffle: host ray permutation, counter-RNG jitter, seeded
@@ -156,8 +171,7 @@ def psnr_replay(o, d, rgbs, dev, n_steps: int, grid0, ho, hd, hrgb):
         return None
     ref = gold["runs"][0]["psnr"].get(str(n_steps))
     if ref is None:
-        return {"step": n_steps, "reference": None, "note": "tests/golden/G21_psnr_bench.json holds steps " + ", ".join(sorted(gold["runs"][0]["psnr"], key=int))
-                + " (the driver's --warmup 5 --steps 20 ends on 65, the defaults on 70)"}
+        return {"step": n_steps, "reference": None, "note": "tests/golden/G21_psnr_bench.json holds steps " + ", ".join(sorted(gold["runs"][0]["psnr"], key=int))}
     cfg = TrainConfig(method="kplanes", scene_type="aabb", batch_size=1024, n_samples=1024, seed=0, host_shuffle=True)
     t2 = Trainer(cfg, o, d, rgbs, torch.ones(3, device=dev), dev)
     t2.occupancy_grid.grid.copy_(grid0)
@@ -194,7 +208,10 @@ def parse():
                     "128 occupancy refreshes) on this workload; prints its own JSON line (time to train, held-out PSNR, step-time extremes)")
     ap.add_argument("--other-steps", type=int, default=8, help="steps per window of the Vanilla / Cobafa side runs")
     ap.add_argument("--other-windows", type=int, default=3)
-    ap.add_argument("--windows", type=int, default=3, help="timed windows of --steps steps each; the first one is the measurement")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps steps each; the first one is the measurement, the "
+                    "others (variance) time every modelled launch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed "
+                    "(loss, batch counts, parameters, occupancy grid) as DIR/<name>.npy")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="N > 1: weak = every rank runs the recipe's batch (B rays x S per loader batch, ~B*S samples per rank and step); "
                          "strong = the recipe's B*S samples per step are split over the ranks (PSNR@step comparable with N = 1)")
@@ -238,12 +255,14 @@ class KernelTimer:
         self.only = None            # a set of tags: only these are timed (the measured window times the dominant launch alone)
         L.call = timed_call
 
-    def summary(self):
+    def summary(self, steps: int = 1):
+        """per tag over the `steps` steps the records were taken in"""
         out = {}
         for tag, recs in self.records.items():
             ms = [e0.elapsed_time(e1) for e0, e1, _ in recs]
             rows = [r for _, _, r in recs]
-            out[tag] = dict(launches=len(ms), total_ms=sum(ms), avg_ms=sum(ms) / len(ms), avg_rows=sum(rows) / len(rows))
+            out[tag] = dict(launches=len(ms), total_ms=sum(ms), ms_per_step=sum(ms) / steps, avg_ms=sum(ms) / len(ms),
+                            avg_rows=sum(rows) / len(rows))
         return out
 
 
@@ -332,6 +351,36 @@ def alloc_counters():
     st = torch.cuda.memory_stats()
     return {"device_allocs": int(st.get("num_device_alloc", 0)), "alloc_retries": int(st.get("num_alloc_retries", 0)),
             "segments": int(st.get("segment.all.current", 0)), "reserved_gb": st.get("reserved_bytes.all.current", 0) / 2 ** 30}
+
+
+DUMP_SAMPLE = 1 << 20          # entries kept of a parameter larger than this (a fixed, seeded sample)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(tr, out_dir: str, rank: int):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy: `loss` (float64 [1], MSE + regulariser of the
+    step), `batch` (float64 [3]: packed samples, rays, loader batches of the step's dynamic batch), `param.<name>` (float32: every
+    parameter after the optimizer step, in logical order; of the larger planes the entries at 2^20 sorted indices drawn by
+    numpy.random.default_rng(0)) and `occupancy_grid` (float32 [128, 128, 128]).  Every rank takes part (the loss is reduced over
+    them); rank 0 writes."""
+    import numpy as np
+    loss = tr.loss_device().double().cpu().numpy()
+    if rank != 0:
+        return
+    arrays = {"loss": loss, "batch": np.array([tr.last["n_samples"], tr.last["n_rays"], tr.last["k"]], np.float64)}
+    for name, p in tr.renderer.named_parameters():
+        v = p.detach().float()
+        if v.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(v.numel(), DUMP_SAMPLE, replace=False))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        arrays["param." + name] = v.cpu().numpy()
+    arrays["occupancy_grid"] = tr.occupancy_grid.grid.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def side_profile(method):
@@ -651,17 +700,19 @@ def main():
 
     # Event pairs around EVERY modelled launch cost the step ~0.2 ms (ten records per step, each a marker the queue drains to):
     # 3.29 against 3.10 ms on one box.  So the last warm-up steps time all of them to find the dominant launch, the measured window
-    # times only that one (two records per step: `roofline`), and the first variance window times the rest (`rooflines`).
-    pre = min(args.warmup, 4) if args.windows >= 2 else 0
+    # times only that one (two records per step: `roofline`), and the rest (`rooflines`) keep the times of those warm-up steps -- or,
+    # with --windows > 1, of the first variance window.
+    pre = min(args.warmup, 4)
     for i in range(args.warmup):
         timer.enabled = i >= args.warmup - pre
         tr.step()
     timer.enabled = False
     dominant = None
+    ks_warmup = {}
     if pre:
         torch.cuda.synchronize()
-        ps = timer.summary()
-        dominant = max(ps, key=lambda t: ps[t]["total_ms"]) if ps else None
+        ks_warmup = timer.summary(pre)
+        dominant = max(ks_warmup, key=lambda t: ks_warmup[t]["total_ms"]) if ks_warmup else None
         timer.records = {}
         timer.only = {dominant} if dominant else None
 
@@ -690,11 +741,13 @@ def main():
     dt, samples, rays_n = window(True)            # THE measurement: `value`, `ms_per_step`, kernel events
     alloc_w0, grown_w0 = alloc_counters()["device_allocs"] - a0, arenas_grown(tr) - g0
     loss = tr.loss_value()
-    ks_measured = timer.summary()
+    ks_measured = timer.summary(args.steps)
     if dominant is not None:
         timer.records, timer.only = {}, None
     extra_windows = [window(dominant is not None and i == 0) for i in range(max(0, args.windows - 1))]      # variance (+ the other launches' events)
     window_ms = [dt / args.steps * 1e3] + [w[0] / args.steps * 1e3 for w in extra_windows]
+    if args.dump_outputs:                          # before anything below touches the trainer (batches, gradients, grid)
+        dump_outputs(tr, args.dump_outputs, rank)
 
     # PSNR@step (the second half of BASELINE.json's metric, run.py:53-54): one held-out 800x800 view of the same synthetic
     # scene -- a camera no rank trains on -- rendered with the parameters as they are after the timed steps (every rank holds the
@@ -716,11 +769,12 @@ def main():
                         "view": "held-out 800x800 camera (rays.synthetic_scene(n_views=1, seed=10007)), inference path (training=False sampling)",
                         "samples_per_step": samples / args.steps,
                         "note": "psnr = the TIMED trainer (device-side shuffle: its ray order is its own); `replay` = a second trainer on the "
-                                "replayable streams, held against the CPU port of the reference's train() on this very configuration"}
+                                "replayable streams, held against the CPU port of the reference's train() on this very configuration at replay.step "
+                                "(the first step of tests/golden/G21_psnr_bench.json at or after `step`)"}
         del img
         if world == 1 and args.views == 20:
             try:
-                psnr_at_step["replay"] = psnr_replay(o, d, rgbs, dev, tr.train_step, grid0, ho, hd, hrgb)
+                psnr_at_step["replay"] = psnr_replay(o, d, rgbs, dev, replay_step(tr.train_step) or tr.train_step, grid0, ho, hd, hrgb)
             except Exception as e:                                  # noqa: BLE001 -- the headline line must still be printed
                 psnr_at_step["replay"] = {"error": repr(e)}
     # the occupancy refresh (run.py:248-249) runs every 16 * 4096 / B steps: a window of K < 64 steps behind a short warm-up
@@ -787,8 +841,8 @@ def main():
             torch.cuda.empty_cache()
 
     if rank == 0:
-        ks = timer.summary()              # every modelled launch (window 1 when the measured window timed the dominant one alone) ...
-        ks.update(ks_measured)            # ... and the dominant launch from the measured window itself
+        ks = timer.summary(args.steps) or ks_warmup     # every modelled launch (window 1, or the last warm-up steps, when the measured
+        ks.update(ks_measured)                          # window timed the dominant one alone) ... and the dominant launch from that window
         pmc, PMC_PROFILE = load_first(PMC_PROFILES)
         mfma, MFMA_PROFILE = load_first(MFMA_PROFILES)
 
@@ -817,7 +871,7 @@ def main():
             sec = k["avg_ms"] * 1e-3
             traffic = pmc.get("per_entry", {}).get(tag) if pmc else None
             cls, limit = launch_class(tag, mode, lean)
-            r = {"kernel": tag, "kernels": kernels, "avg_launch_ms": k["avg_ms"], "ms_per_step": k["total_ms"] / args.steps,
+            r = {"kernel": tag, "kernels": kernels, "avg_launch_ms": k["avg_ms"], "ms_per_step": k["ms_per_step"],
                  **({"shares_the_chip": "TN_ADAM_OVERLAP: tn_adam_reg_multi (side stream) runs beside the first weight-gradient launch; serial: "
                                         "0.22 ms / 0.83 ms"} if (_run_mod.ADAM_OVERLAP and world == 1 and tag in ("tn_adam_reg_multi", "tn_kplanes_mlp_bwd_pair:wgrad")) else {}),
                  "rows_per_launch": k["avg_rows"], "row": unit, "algorithmic_per_row": unit_work, "traffic": traffic,
@@ -858,7 +912,7 @@ def main():
 
         step_ms = dt / args.steps * 1e3
         # every timed launch that is >= 5 % of the step, largest first; `roofline` = the dominant one
-        roofs = [roofline_of(t) for t in sorted(ks, key=lambda t: -ks[t]["total_ms"]) if ks[t]["total_ms"] / args.steps >= 0.05 * step_ms]
+        roofs = [roofline_of(t) for t in sorted(ks, key=lambda t: -ks[t]["ms_per_step"]) if ks[t]["ms_per_step"] >= 0.05 * step_ms]
         roof = roofs[0] if roofs else None
         per_gpu_samples = samples / args.steps / world
         whole = {"mfma_tflops": FLOP_STEP * per_gpu_samples / (step_ms * 1e-3) / 1e12,
@@ -877,14 +931,15 @@ def main():
         # <= 1 KB: what a reader of the driver's record needs first (repeated as the LAST key: a tail of the line keeps it as well)
         oc = others or {}
         summary = {"value": samples / dt, "ms_per_step": step_ms, "windows_median_ms": srt[len(srt) // 2], "matmul": mode, "lean": lean,
-                   "kernels_ms": {t.replace("tn_kplanes_mlp_", "").replace("tn_", ""): round(v["total_ms"] / args.steps, 4) for t, v in sorted(ks.items())},
+                   "kernels_ms": {t.replace("tn_kplanes_mlp_", "").replace("tn_", ""): round(v["ms_per_step"], 4) for t, v in sorted(ks.items())},
                    "other_ms": {k: round(v["ms_per_step"], 3) for k, v in oc.items() if isinstance(v, dict) and "ms_per_step" in v},
                    "other_render_ms": {k: round(v["render_ms"], 1) for k, v in oc.items() if isinstance(v, dict) and "render_ms" in v},
                    "render_fwd_samples_per_s": stages["render_fwd_samples_per_s"] if stages else None,
                    "sampler_samples_per_s": stages["sampler_samples_per_s"] if stages else None,
                    "psnr": ({"step": psnr_at_step["step"], "timed_run": round(psnr_at_step["psnr"], 3),
-                             **({k: (round(v, 4) if isinstance(v, float) else v) for k, v in (psnr_at_step.get("replay") or {}).items()
-                                 if k in ("psnr", "reference", "delta_db")})} if psnr_at_step else None),
+                             **({("replay_step" if k == "step" else k): (round(v, 4) if isinstance(v, float) else v)
+                                 for k, v in (psnr_at_step.get("replay") or {}).items() if k in ("step", "psnr", "reference", "delta_db")})}
+                            if psnr_at_step else None),
                    "hbm_bytes_per_step": whole.get("hbm_bytes_per_step"), "dominant": roof["kernel"] if roof else None,
                    "dominant_bound": roof["bound"] if roof else None, "dominant_frac": roof["frac"] if roof else None,
                    # the same step with every product on v_mfma_f32_32x32x2_f32 (other_configs.kplanes_fp32_heads): the conservative figure
@@ -922,11 +977,16 @@ def main():
                                    if refresh else None),
             "stages": stages,
             "other_configs": others,
-            "kernel_timing": {"measured_window": sorted(ks_measured), "window_1": sorted(t for t in ks if t not in ks_measured),
-                              "note": "HIP-event pairs on the launch stream: window 0 around the dominant launch only, window 1 around every modelled launch"},
+            "kernel_timing": {"measured_window": sorted(ks_measured), "other_launches": sorted(t for t in ks if t not in ks_measured),
+                              "other_launches_from": None if dominant is None else "window 1" if len(window_ms) > 1 else f"the last {pre} warm-up steps",
+                              "warmup_ms_per_step": {t: round(v["ms_per_step"], 4) for t, v in sorted(ks_warmup.items())},
+                              "warmup_steps_timed": pre,
+                              "note": "HIP-event pairs on the launch stream: window 0 around the dominant launch only, window 1 (--windows > 1) "
+                                      "or else the last warm-up steps around every modelled launch"},
             "windows": {"n": len(window_ms), "steps_each": args.steps, "ms_per_step": window_ms, "min": srt[0], "median": srt[len(srt) // 2],
-                        "note": "window 0 = value; window 1 carries all launch events; the window that contains step 64 the occupancy refresh"},
-            "kernels_ms_per_step": {t: v["total_ms"] / args.steps for t, v in sorted(ks.items())},
+                        "note": "window 0 = value; with --windows > 1, window 1 carries all launch events (else the last warm-up steps do: "
+                                "kernel_timing); the window that contains step 64 the occupancy refresh"},
+            "kernels_ms_per_step": {t: v["ms_per_step"] for t, v in sorted(ks.items())},
             "allocator": dict(alloc_counters(), device_allocs_in_window0=alloc_w0, arenas_grown_in_window0=grown_w0),
             "roofline": roof,
             "rooflines": roofs,

@@ -148,10 +148,11 @@ def test_psnr_at_step_on_the_reference_trajectory_deep_stacks(golden, tight_unti
 def test_psnr_at_step_on_the_headline_configuration(heads_mode, monkeypatch):
     """G21 (round 5): PSNR@step pinned on the configuration BASELINE.json's metric is quoted on -- bench.py's 20 synthetic 800 x 800
     cameras, B = 1024 rays x S = 1024, its occupancy ball, seed 0 -- against the CPU port of the reference's train() on the same replayable
-    streams (oracle/make_psnr_curve.py --bench, ~1 h of CPU).  After the driver's 5 + 3 x 20 = 65 steps (across the occupancy refresh at
+    streams (oracle/make_psnr_curve.py --bench, ~1 h of CPU).  After 65 steps (across the occupancy refresh at
     step 64) the held-out 800 x 800 view must agree within the north star's 0.1 dB, in both head forms (f16x2: the default, with the lean
     backward of round 5; fp32: the stash form on the fp32 MFMA); the first dynamic batches must have the golden's sizes and the loss of
-    the last step agree to 2 %.  bench.py prints the same comparison as psnr_at_step.replay."""
+    the last step agree to 2 %.  bench.py prints the same comparison as psnr_at_step.replay, at the first golden step at or after its
+    timed run's last one."""
     import importlib.util
     from tinynerf_amd import models, rays
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -56,8 +56,9 @@ def test_independent_stream_golden_is_well_formed():
 
 
 def test_headline_configuration_golden_is_well_formed():
-    """G21 (oracle/make_psnr_curve.py --bench): the replay run on bench.py's own configuration -- the step counts the bench ends on are
-    there, the recipe learns, and the batch rule lands on ~2^20 samples per step."""
+    """G21 (oracle/make_psnr_curve.py --bench): the replay run on bench.py's own configuration -- the steps bench.py's replay walks to are
+    there (bench.replay_step: 30 after the driver's --warmup 5 --steps 20 and after the defaults, 65 with --windows 3), the recipe
+    learns, and the batch rule lands on ~2^20 samples per step."""
     g = json.load(open(os.path.join(ROOT, "tests", "golden", "G21_psnr_bench.json")))
     mk = _maker()
     assert g["replay"] and g["config"] == mk.BENCH_CONFIG and g["steps"] == 70 and g["eval_at"] == list(mk.BENCH_EVAL_AT)
