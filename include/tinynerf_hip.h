@@ -72,6 +72,15 @@ int tn_composite_fwd(const float *rgbs, const float *weights, const int32_t *inf
 int tn_composite_bwd(const float *rgbs, const float *weights, const int32_t *info, const float *bg,
                      const float *grad_rendered, float *grad_rgbs, float *grad_weights,
                      int64_t n_samples, int64_t n_rays, void *stream);
+/* Per-ray maps of the rendered weights w_k and sample distances t_k (tn_sample_pack_t) of ray r, k = 0..count-1:
+ *   opacity[r]      = sum_k w_k (bit-identical to tn_composite_fwd's opacity: same lane order, same reduction tree);
+ *   depth[r]        = sum_k w_k t_k / opacity[r]   (expected depth given a hit), 0 when opacity[r] == 0;
+ *   median_depth[r] = t_j of the first j with sum_{k<=j} w_k >= opacity[r] / 2, 0 when opacity[r] == 0.
+ * Rays without samples get 0 in all three.  Each output may be NULL; t_values may be NULL when depth and median_depth are.
+ * One wave per ray; info must be 8-byte aligned.  No reference call site: the reference computes the opacity only to blend
+ * the background (core.py:262-265) and returns neither map. */
+int tn_ray_maps(const float *weights, const float *t_values, const int32_t *info, int64_t n_rays, float *opacity,
+                float *depth, float *median_depth, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * a5/a6  occupancy grid                                        (reference core.py:93-156)
@@ -157,6 +166,15 @@ int tn_sample_pack(const tn_sampler_desc *desc, const float *rays_o, const float
                    int64_t n_rays, const uint64_t *maskbits, const int32_t *info,
                    const int32_t *base_offset, float *packed, int32_t *ray_ids, float *steps, int64_t capacity,
                    void *stream);
+/* tn_sample_pack that also writes t_values[row] (may be NULL, [capacity]): the ray parameter t at which the packed sample was
+ * taken, jitter included -- t_min + k*step (+ jitter*step) for the AABB marcher, t_table[k] (+ jitter*delta_k) for the unbounded
+ * one (core.py:84-85, 52-58, 173).  The rays are unit length (data.py), so t is a distance in world units.  Every other output is
+ * the same as tn_sample_pack's, bit for bit (the same kernel).  No reference call site: the reference drops t after
+ * core.py:174; it feeds tn_ray_maps. */
+int tn_sample_pack_t(const tn_sampler_desc *desc, const float *rays_o, const float *rays_d,
+                     int64_t n_rays, const uint64_t *maskbits, const int32_t *info,
+                     const int32_t *base_offset, float *packed, int32_t *ray_ids, float *steps, float *t_values,
+                     int64_t capacity, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * a9  positional encoding                                      (reference models.py:30-39)

@@ -310,10 +310,14 @@ class RayProvider:
 
     @torch.no_grad()
     def __call__(self, rays_o: torch.Tensor, rays_d: torch.Tensor, training: bool,
-                 jitter: Optional[torch.Tensor] = None, return_ray_ids: bool = False):
+                 jitter: Optional[torch.Tensor] = None, return_ray_ids: bool = False, return_t: bool = False):
         """packed_samples [N,7] = (contracted xyz, ray dir, step), packing_info [R,2] int32 =
         (start,count) -- core.py:165-188.  ``jitter`` ([R,S] U[0,1)) replaces the device RNG that
-        stands in for ``torch.rand_like`` when ``training`` (parity runs)."""
+        stands in for ``torch.rand_like`` when ``training`` (parity runs).
+
+        Returns ``(packed, info)``, then ``ray_ids [N] int32`` if ``return_ray_ids``, then ``t [N]`` if ``return_t``:
+        the ray parameter each sample was taken at, jitter included (a distance: rays are unit length), for
+        ``NerfRenderer.render_maps``."""
         o, d = _f32c(rays_o), _f32c(rays_d)
         dev = L.require_cuda(o, d, self.occupancy_grid.grid)
         R = o.size(0)
@@ -332,11 +336,15 @@ class RayProvider:
         n = int(total.item())                      # the one host sync: the output shape
         packed = torch.empty((n, 7), device=dev)
         ray_ids = torch.empty(n, dtype=torch.int32, device=dev) if return_ray_ids else None
-        L.call("tn_sample_pack", dev, C.byref(desc), L.ptr(o), L.ptr(d), C.c_int64(R), L.ptr(maskbits), L.ptr(info),
-               C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), C.c_void_p(None), C.c_int64(n))
-        if return_ray_ids:
-            return packed, info, ray_ids
-        return packed, info
+        if return_t:
+            t = torch.empty(n, device=dev)
+            L.call("tn_sample_pack_t", dev, C.byref(desc), L.ptr(o), L.ptr(d), C.c_int64(R), L.ptr(maskbits), L.ptr(info),
+                   C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), C.c_void_p(None), L.ptr(t), C.c_int64(n))
+        else:
+            L.call("tn_sample_pack", dev, C.byref(desc), L.ptr(o), L.ptr(d), C.c_int64(R), L.ptr(maskbits), L.ptr(info),
+                   C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), C.c_void_p(None), C.c_int64(n))
+        out = (packed, info) + ((ray_ids,) if return_ray_ids else ()) + ((t,) if return_t else ())
+        return out
 
 
 # --------------------------------------------------------------------------------------------
@@ -467,6 +475,50 @@ class NerfRenderer(torch.nn.Module):
             else:
                 rgb_active = self.rgb_decoder(feats[active], packed_samples[:, 3:6][active])
                 rgbs = torch.zeros((n_samples, 3), device=device).index_copy(0, active, rgb_active)
+        handout = self.__dict__.get("_stats", {}).get("maps_handout")
+        if handout is not None:             # render_maps: the weights this forward composites with
+            handout["weights"] = weights
         if n_rays == 0:
             return torch.zeros((0, 3), device=device)
         return _Composite.apply(rgbs, weights, packing_info.contiguous(), bg)
+
+    @torch.no_grad()
+    def _maps(self, weights: torch.Tensor, packing_info: torch.Tensor, t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        R = packing_info.size(0)
+        dev = packing_info.device
+        opacity, depth, median = (torch.zeros(R, device=dev) for _ in range(3))
+        if R > 0 and weights.numel() > 0:
+            w, info, t = _f32c(weights), packing_info.contiguous(), _f32c(t)
+            L.require_cuda(w, info, t)
+            L.call("tn_ray_maps", dev, L.ptr(w), L.ptr(t), L.ptr(info), C.c_int64(R), L.ptr(opacity), L.ptr(depth), L.ptr(median))
+        return opacity, depth, median
+
+    def render_maps(
+        self,
+        packed_samples: torch.Tensor,  # [n_samples, 7]
+        packing_info: torch.Tensor,  # [n_rays, 2]
+        t: torch.Tensor,  # [n_samples], RayProvider(..., return_t=True)
+        early_termination_threshold: float = 1e-4,
+    ) -> dict:
+        """Inference: ``forward``'s colour plus per-ray maps of the weights it composited with, as a dict of
+        ``rgb [R,3]`` (bit-identical to ``forward``), ``opacity [R]`` (sum of the weights), ``depth [R]`` (expected
+        depth given a hit: sum w t / opacity) and ``median_depth [R]`` (t where the weights' prefix reaches half the
+        opacity); rays with opacity 0 get depth 0.  Same dispatch as ``forward`` (fused nodes or the module path);
+        the weights are handed out by that forward, not recomputed (``tn_ray_maps``).  The maps carry no gradient:
+        call it under ``torch.no_grad()`` when parameters require grad."""
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("NerfRenderer.render_maps is inference only: call it under torch.no_grad()")
+        if t.dim() != 1 or t.size(0) != packed_samples.size(0):
+            raise RuntimeError("t must hold one value per packed sample (RayProvider(..., return_t=True))")
+        stats = self.__dict__.setdefault("_stats", {})
+        handout: dict = {}
+        stats["maps_handout"] = handout
+        try:
+            rgb = self.forward(packed_samples, packing_info, early_termination_threshold)
+        finally:
+            stats.pop("maps_handout", None)
+        weights = handout.get("weights")
+        if weights is None:
+            weights = torch.zeros(0, device=packed_samples.device)
+        opacity, depth, median = self._maps(weights.detach(), packing_info, t)
+        return {"rgb": rgb, "opacity": opacity, "depth": depth, "median_depth": median}

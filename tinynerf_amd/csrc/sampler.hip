@@ -142,12 +142,12 @@ __device__ __forceinline__ bool contract(const SamplerArgs &a, const float p[3],
     return inside;
 }
 
-// One candidate: returns keep flag; fills contracted coords and the step size.
+// One candidate: returns keep flag; fills contracted coords, the step size and the ray parameter t the point was taken at
+// (jitter included).
 template <int MARCH, int CONTRACT>
 __device__ __forceinline__ bool candidate(const SamplerArgs &a, const float o[3], const float d[3], float t_min,
-                                          int64_t ray, int k, float c[3], float &delta)
+                                          int64_t ray, int k, float c[3], float &delta, float &t)
 {
-    float t;
     march_t<MARCH>(a, t_min, k, t, delta);
     if (a.jitter) {
         t = t + a.jitter[ray * a.n_samples + k] * delta;    // core.py:173
@@ -243,9 +243,9 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void sample_mask_kernel(
     int count = 0;
     for (int ch = 0; ch < n_active; ++ch) {
         const int k = ch * 64 + lane;
-        float c[3], delta;
+        float c[3], delta, t;
         bool keep = false;
-        if (k < a.n_samples) keep = candidate<MARCH, CONTRACT>(a, o, d, t_min, ray, k, c, delta);
+        if (k < a.n_samples) keep = candidate<MARCH, CONTRACT>(a, o, d, t_min, ray, k, c, delta, t);
         const uint64_t m = __ballot(keep);
         if (lane == 0) maskbits[ray * n_chunks + ch] = m;
         count += __popcll(m);
@@ -446,7 +446,8 @@ template <int MARCH, int CONTRACT>
 __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void sample_pack_kernel(
     SamplerArgs a, const float *__restrict__ rays_o, const float *__restrict__ rays_d, int64_t n_rays,
     const uint64_t *__restrict__ maskbits, const int32_t *__restrict__ info, const int32_t *__restrict__ base_offset,
-    float *__restrict__ packed, int32_t *__restrict__ ray_ids, float *__restrict__ steps, int64_t capacity)
+    float *__restrict__ packed, int32_t *__restrict__ ray_ids, float *__restrict__ steps, int64_t capacity,
+    float *__restrict__ t_values)
 {
     const int lane = tn::lane_id();
     const int64_t ray = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
@@ -464,8 +465,8 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void sample_pack_kernel(
         if (m == 0) continue;
         if ((m >> lane) & 1ull) {
             const int k = ch * 64 + lane;
-            float c[3], delta;
-            (void)candidate<MARCH, CONTRACT>(a, o, d, t_min, ray, k, c, delta);
+            float c[3], delta, t;
+            (void)candidate<MARCH, CONTRACT>(a, o, d, t_min, ray, k, c, delta, t);
             const int64_t row = out + tn::rank_below(m);
             if (row < capacity) {
                 float *p = packed + 7 * row;
@@ -474,6 +475,7 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void sample_pack_kernel(
                 p[6] = delta;
                 if (ray_ids) ray_ids[row] = (int32_t)ray;
                 if (steps) steps[row] = delta;
+                if (t_values) t_values[row] = t;
             }
         }
         out += __popcll(m);
@@ -687,9 +689,9 @@ extern "C" int tn_batch_plan_scan(const int32_t *counts, int64_t n_rays, int32_t
     return n_rays ? tn_sample_scan(counts, n_rays, nullptr, info, nullptr, stream) : TN_OK;
 }
 
-extern "C" int tn_sample_pack(const tn_sampler_desc *desc, const float *rays_o, const float *rays_d, int64_t n_rays,
-                              const uint64_t *maskbits, const int32_t *info, const int32_t *base_offset, float *packed,
-                              int32_t *ray_ids, float *steps, int64_t capacity, void *stream)
+extern "C" int tn_sample_pack_t(const tn_sampler_desc *desc, const float *rays_o, const float *rays_d, int64_t n_rays,
+                                const uint64_t *maskbits, const int32_t *info, const int32_t *base_offset, float *packed,
+                                int32_t *ray_ids, float *steps, float *t_values, int64_t capacity, void *stream)
 {
     SamplerArgs a;
     if (int rc = make_args(desc, a)) return rc;
@@ -697,8 +699,15 @@ extern "C" int tn_sample_pack(const tn_sampler_desc *desc, const float *rays_o, 
     if (n_rays == 0 || capacity == 0) return TN_OK;
     TN_REQUIRE(rays_o && rays_d && maskbits && info && packed, TN_E_NULL, "tn_sample_pack: null pointer");
     TN_DISPATCH_MC(a, sample_pack_kernel<M, Cn><<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(
-                          a, rays_o, rays_d, n_rays, maskbits, info, base_offset, packed, ray_ids, steps, capacity));
+                          a, rays_o, rays_d, n_rays, maskbits, info, base_offset, packed, ray_ids, steps, capacity, t_values));
     return tn::check_launch("sample_pack_kernel");
+}
+
+extern "C" int tn_sample_pack(const tn_sampler_desc *desc, const float *rays_o, const float *rays_d, int64_t n_rays,
+                              const uint64_t *maskbits, const int32_t *info, const int32_t *base_offset, float *packed,
+                              int32_t *ray_ids, float *steps, int64_t capacity, void *stream)
+{
+    return tn_sample_pack_t(desc, rays_o, rays_d, n_rays, maskbits, info, base_offset, packed, ray_ids, steps, nullptr, capacity, stream);
 }
 
 extern "C" int tn_occupancy_query(const float *grid, int D, int H, int W, const float *coords, int64_t n, float threshold,

@@ -270,9 +270,63 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void ray_aux_kernel(const flo
     }
 }
 
+// Per-ray opacity, expected depth and median depth from the weights and the sample distances t (tn_sample_pack_t).
+// Pass 1: opacity = sum w and sum w t with composite_fwd_kernel's lane order and wave_sum tree, so the opacity is the bits that
+// kernel writes.  Pass 2 (median only): inclusive prefix of w over chunks of 64 (wave_scan_add + the carry), stopped at the
+// first chunk in which it reaches opacity / 2 -- on a ray that terminated early that is one of its first chunks.
+__global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void ray_maps_kernel(
+    const float *__restrict__ weights, const float *__restrict__ t_values, const int32_t *__restrict__ info, int64_t n_rays,
+    float *__restrict__ opacity, float *__restrict__ depth, float *__restrict__ median_depth)
+{
+    const int lane = tn::lane_id();
+    const int64_t ray = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int2 sc = reinterpret_cast<const int2 *>(info)[ray];
+    float o = 0.f, wt = 0.f;
+    for (int k = lane; k < sc.y; k += 64) {
+        const float w = weights[sc.x + k];
+        o += w;
+        if (depth) wt += w * t_values[sc.x + k];
+    }
+    o = tn::wave_sum(o);
+    if (depth) wt = tn::wave_sum(wt);
+    float med = 0.f;
+    if (median_depth && o > 0.f) {
+        const float half = 0.5f * o;
+        float carry = 0.f;
+        int found = -1;
+        for (int base = 0; base < sc.y; base += 64) {
+            const int k = base + lane;
+            const float p = carry + wave_scan_add(k < sc.y ? weights[sc.x + k] : 0.f, lane);
+            const uint64_t hit = __ballot(k < sc.y && p >= half);
+            if (hit) { found = base + __builtin_ctzll(hit); break; }
+            carry = __shfl(p, 63, 64);
+        }
+        // (a prefix that never reaches the mark -- fp32 rounding of a sum whose order differs from the opacity's -- ends on the last sample)
+        med = t_values[sc.x + (found >= 0 ? found : sc.y - 1)];
+    }
+    if (lane == 0) {
+        if (opacity) opacity[ray] = o;
+        if (depth) depth[ray] = o > 0.f ? wt / o : 0.f;
+        if (median_depth) median_depth[ray] = med;
+    }
+}
+
 inline unsigned ray_blocks(int64_t n_rays) { return (unsigned)((n_rays + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
 
 }  // namespace
+
+extern "C" int tn_ray_maps(const float *weights, const float *t_values, const int32_t *info, int64_t n_rays, float *opacity,
+                           float *depth, float *median_depth, void *stream)
+{
+    TN_REQUIRE(n_rays >= 0, TN_E_SIZE, "tn_ray_maps: negative size");
+    if (n_rays == 0 || !(opacity || depth || median_depth)) return TN_OK;
+    TN_REQUIRE(weights && info && (t_values || !(depth || median_depth)), TN_E_NULL, "tn_ray_maps: null pointer");
+    TN_REQUIRE(((uintptr_t)info & 7) == 0, TN_E_ALIGN, "tn_ray_maps: info must be 8-byte aligned");
+    ray_maps_kernel<<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(weights, t_values, info, n_rays,
+                                                                                                      opacity, depth, median_depth);
+    return tn::check_launch("ray_maps_kernel");
+}
 
 extern "C" int tn_weights_fwd(const float *sigmas, const float *steps, const int32_t *info, float threshold,
                               float *weights, int64_t n_samples, int64_t n_rays, void *stream)

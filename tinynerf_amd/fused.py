@@ -258,6 +258,8 @@ class _RenderKPlanes(Function):
             stats["gate"] = ctx.gate
             stats["pre_gated"] = ctx.gate_in_slot        # the caller MAY hand in a gated gradient (and must then say so)
             stats["upstream_gated"] = False
+            if stats.get("maps_handout") is not None:   # NerfRenderer.render_maps: the weights this forward composited with
+                stats["maps_handout"]["weights"] = weights
         ctx.save_for_backward(packed, info, bg, freqs, feat, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params)
         ctx.cfg = (n_freqs, n_planes, n_sigma, accumulate, stride, sb, rb, covered)
         ctx.lean = lean
@@ -504,6 +506,8 @@ class _RenderHeads(Function):
             stats["gate"] = ctx.gate
             stats["pre_gated"] = ctx.gate_in_slot
             stats["upstream_gated"] = False
+            if stats.get("maps_handout") is not None:   # (see _RenderKPlanes)
+                stats["maps_handout"]["weights"] = weights
         ctx.save_for_backward(feat, info, bg, freqs, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params)
         ctx.cfg = (n_freqs, n_sigma, accumulate, stride, sb, rb, covered)
         ctx.arena = arena

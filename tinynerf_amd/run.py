@@ -742,12 +742,19 @@ class Trainer:
 
     # ------------------------------------------------------------------ inference (run.py:15-50)
     @torch.no_grad()
-    def render_rays(self, rays_o: torch.Tensor, rays_d: torch.Tensor, batch_size: Optional[int] = None) -> torch.Tensor:
+    def render_rays(self, rays_o: torch.Tensor, rays_d: torch.Tensor, batch_size: Optional[int] = None, maps: bool = False):
+        """rgb [R,3]; with ``maps`` the dict of ``NerfRenderer.render_maps`` (rgb [R,3], opacity, depth, median_depth [R])"""
         self.renderer.eval()
         # rays are independent: the chunk size does not change a single output bit.  The reference walks an image in chunks of
         # the training batch size (run.py:35-43: 625 calls per 800x800 image), which makes every launch tiny: 139 ms per
         # K-Planes image against 25 ms in 2^16-ray chunks (7 GiB of scratch at S = 1024; scripts/infer_chunks.py)
         bs = batch_size or max(self.cfg.batch_size, 1 << 16)
+        if maps:
+            parts = []
+            for k in range(0, rays_o.size(0), bs):
+                samples, info, t = self.ray_provider(rays_o[k:k + bs], rays_d[k:k + bs], training=False, return_t=True)
+                parts.append(self.renderer.render_maps(samples, info, t))
+            return {key: torch.cat([p[key] for p in parts], 0) for key in ("rgb", "opacity", "depth", "median_depth")}
         out = []
         for k in range(0, rays_o.size(0), bs):
             samples, info = self.ray_provider(rays_o[k:k + bs], rays_d[k:k + bs], training=False)
@@ -766,18 +773,47 @@ class EvalMetrics:
 
 
 @torch.no_grad()
-def infer(trainer: "Trainer", dataset, indices: List[int], folder=None, name: str = "render", batch_size: Optional[int] = None):
-    """Render whole images (run.py:15-50); PNGs are written when `folder` is given."""
+def infer(trainer: "Trainer", dataset, indices: List[int], folder=None, name: str = "render", batch_size: Optional[int] = None,
+          maps: bool = False):
+    """Render whole images (run.py:15-50); PNGs are written when `folder` is given.
+
+    ``maps``: each entry of the result is the dict of ``Trainer.render_rays(maps=True)`` shaped as the image (rgb [H,W,3],
+    opacity / depth / median_depth [H,W]) instead of the image alone, and with `folder` these files are written as well:
+    ``{name}_depth_{i:04d}.png`` (16-bit grayscale, expected depth / the image's largest expected depth),
+    ``{name}_opacity_{i:04d}.png`` (16-bit grayscale, opacity in [0, 1]) and ``{name}_maps_{i:04d}.npz`` (float32 depth,
+    median_depth, opacity and the PNG's depth_scale)."""
     out = []
     for i in indices:
         item = dataset[i]
         o, d = item["rays_o"].reshape(-1, 3).to(trainer.device), item["rays_d"].reshape(-1, 3).to(trainer.device)
-        img = trainer.render_rays(o, d, batch_size).reshape(*item["rays_o"].shape[:-1], 3)
-        out.append(img)
+        hw = item["rays_o"].shape[:-1]
+        res = trainer.render_rays(o, d, batch_size, maps=maps)
+        if maps:
+            res = {k: v.reshape(*hw, *v.shape[1:]) for k, v in res.items()}
+            img = res["rgb"]
+        else:
+            img = res.reshape(*hw, 3)
+        out.append(res if maps else img)
         if folder is not None:
             from PIL import Image
             Image.fromarray((255. * img).clamp(0, 255).to(torch.uint8).cpu().numpy()).save(folder / f"{name}_{i:04d}.png")
+            if maps:
+                _save_maps(res, folder, name, i)
     return out
+
+
+def _save_maps(res: Dict[str, torch.Tensor], folder, name: str, i: int) -> None:
+    import numpy as np
+    from PIL import Image
+    host = {k: res[k].float().cpu().numpy() for k in ("depth", "median_depth", "opacity")}
+    scale = float(host["depth"].max()) if host["depth"].size else 0.0
+
+    def png16(x: "np.ndarray", path) -> None:
+        Image.fromarray(np.round(np.clip(x, 0.0, 1.0) * 65535.0).astype(np.uint16)).save(path)
+
+    png16(host["depth"] / scale if scale > 0 else host["depth"], folder / f"{name}_depth_{i:04d}.png")
+    png16(host["opacity"], folder / f"{name}_opacity_{i:04d}.png")
+    np.savez(folder / f"{name}_maps_{i:04d}.npz", depth_scale=np.float32(scale), **host)
 
 
 def evaluate(dataset, rendered: List[torch.Tensor], indices: List[int]) -> List[EvalMetrics]:
@@ -790,8 +826,10 @@ def evaluate(dataset, rendered: List[torch.Tensor], indices: List[int]) -> List[
 
 
 def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=None, eval_every: Optional[int] = None,
-          eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100):
-    """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device."""
+          eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
+          render_maps: bool = False):
+    """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device.  ``render_maps``: the final
+    test render also writes the depth / opacity maps of every image (``infer(maps=True)``)."""
     import json
     from dataclasses import asdict
     device = device or train_rays.rays_o.device
@@ -816,7 +854,9 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
     test_metrics = None
     if test_set is not None:
         idx = list(range(len(test_set)))
-        rendered = infer(tr, test_set, idx, output, "test_full")
+        rendered = infer(tr, test_set, idx, output, "test_full", maps=render_maps)
+        if render_maps:
+            rendered = [r["rgb"] for r in rendered]
         if test_set.rgbs:
             test_metrics = [asdict(m) for m in evaluate(test_set, rendered, idx)]
     train_metrics = [{"loss": lv, "occupancy": ov} for lv, ov in log.tolist()]
