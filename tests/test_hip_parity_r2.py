@@ -345,6 +345,19 @@ def test_kplanes_backward_full_resolution_vs_grid_sampler():
             assert np.count_nonzero(r) > 1000
             close_rel_inf(got, r, 1e-5, f"plane {s}.{p}")
             assert np.array_equal(got != 0, r != 0) or np.abs(got[(got != 0) != (r != 0)]).max() < 1e-5 * np.abs(r).max()
+    # per texel against fp64 (test_hip_scatter.py): |got - ref| <= (m + 14) 2^-24 A, A = sum of |terms|, m = taps landing there.
+    # The batch's coordinates are arbitrary fp32, so the reference samples at the source index fp32 computes (as ATen's fp32
+    # grid_sampler does); its fp64 inversion is good to ~2^-45 of a weight, hence the absolute slack.
+    import _scatter_orders as so
+    xn = x.cpu().numpy()
+    xs = [so.source_index_coords(xn, planes[3 * s].size(3)) for s in range(3)]
+    hwc = [p.detach()[0].permute(1, 2, 0).cpu().numpy() for p in planes]
+    _, _, rg, arg = so.kplanes_ref(xs, hwc, gfeat.cpu().numpy())
+    for i, p in enumerate(planes):
+        side = p.size(3)
+        m = so.tap_counts(xs[i // 3], side, side, i % 3)[:, :, None]
+        so.assert_within(p.grad[0].permute(1, 2, 0).cpu().numpy(), rg[i], arg[i], m, 14, f"plane {i}",
+                         atol=2.0 ** -40 * float(arg[i].max()))
 
 
 # ------------------------------------------------------------------------------------------------ a8: tn_batch_plan
