@@ -40,7 +40,6 @@ constexpr int64_t WS_TAIL_BYTES = 256;
 __host__ inline float *ws_tail(float *stash, int64_t total_rows) { return stash + total_rows * 32; }
 // behind the tail: the packed weight stream of the cross-layer forward (mlp_fused_f2.hip), 256-byte aligned
 __host__ inline int64_t fused_pack_offset(int64_t total_rows) { return (total_rows * 128 + WS_TAIL_BYTES + 255) & ~(int64_t)255; }
-__host__ inline void *fused_pack_area(float *stash, int64_t total_rows) { return reinterpret_cast<unsigned char *>(stash) + fused_pack_offset(total_rows); }
 
 __host__ __device__ inline bool plain_x_rows(int H, int n_layers, int enc, int K0_pad, int out_dim) {
     return enc == TN_ENC_NONE && K0_pad <= 64 && H >= 128 && n_layers >= 3 && out_dim > 4 && out_dim <= H;     // (= layer_kernel_path)
@@ -1058,8 +1057,26 @@ int launch_fwd_lds(const FwdLayerArgs &f, int64_t n, float *stash, float *y, hip
     return tn::check_launch("fwd_lds_kernel");
 }
 
-// the layer-kernel training forward (run_fwd_only): one launch per layer, [feature][32-sample] rows between them
-__host__ inline bool layer_kernel_path(int H, int L, int out) { return H >= 128 && L >= 3 && out > 4 && out <= H; }
+// ------------------------------------------------------------------------------------------------
+// host side: the plan of one pass over a wide / deep stack
+// ------------------------------------------------------------------------------------------------
+// make_plan takes every decision of a pass once: the workspace layout and size, the forward's form, where the backward's
+// d loss / d y comes from, and each layer's weight- and data-gradient kernel with its row offsets and tail slots.  run_fwd and
+// run_bwd turn the plan into launches, one launch per step, in order.  Each eligibility rule is one predicate here.
+
+// the layer-kernel path: the first layer, then one launch per layer, [feature][32-sample] rows between them
+__host__ inline bool layer_kernel_path(int H, const MlpArgs &a) { return H >= 128 && a.n_layers >= 3 && a.out_dim > 4 && a.out_dim <= H; }
+// ... whose first layer reads its (encoded) inputs as workspace rows: positional encoding with <= 64 slots, or <= 64 plain inputs
+// (plain_x_rows); these stacks train on the slab layout
+__host__ inline bool input_rows(int H, const MlpArgs &a) {
+    return layer_kernel_path(H, a) && (a.enc == TN_ENC_POSENC || a.enc == TN_ENC_NONE) && a.K0_pad <= 64;
+}
+// ... and can run the cross-layer f16x2 launches of mlp_fused_f2.hip: the data-gradient chain (all its layers H x H) and, without an
+// output activation, the forward in one launch.  Only these workspaces hold the chain's gradient slabs and the packed weight stream.
+__host__ inline bool cross_layer(int H, const MlpArgs &a) { return input_rows(H, a) && a.f2 && !a.layerwise && a.out_dim == H; }
+__host__ inline bool fused_fwd(int H, const MlpArgs &a) { return cross_layer(H, a) && a.out_act == TN_ACT_NONE; }
+// TN_MLP_SKIP_LAST: the training forward stops at the last hidden activation (its consumers took the last layer over)
+__host__ inline bool skip_last_ok(int H, const MlpArgs &a) { return input_rows(H, a) && a.f2 && a.out_dim == H; }
 
 // `inference`: no backward follows, so the hidden activations need not survive: two ping-pong buffers of H rows each (plus the
 // encoded-input rows) instead of one buffer per layer -- (2 H + rowsE) * 128 B per 32 samples (2.3 KB per sample for the
@@ -1094,15 +1111,11 @@ struct RowMap {
     int64_t offGC(int l) const { return gc_off + l * sl; }      // slab layout: d loss / d (pre-activation of hidden layer l), kept for its weight gradient
     int64_t total_rows(int64_t n_tiles) const { return slab ? n_slabs * sl : n_tiles * lay.total; }
 };
-__host__ inline bool slab_eligible(int H, int L, int enc, int in_dim, int K0_pad, int out) {
-    if (!(H == 128 || H == 256) || !layer_kernel_path(H, L, out) || L > TN_MLP_MAX_LAYERS) return false;
-    const Layout lay = make_layout(H, L, enc, in_dim, K0_pad, out);
-    const bool plain = plain_x_rows(H, L, enc, K0_pad, out) && lay.rowsE == 64;
-    return ((enc == TN_ENC_POSENC && K0_pad <= 64) || plain) && lay.rowsG == H && lay.rowsE <= H;
-}
-__host__ inline RowMap make_rowmap(int H, int L, int enc, int in_dim, int K0_pad, int out, int64_t n_tiles, bool slab) {
+// `chain`: + the L - 1 slabs of the cross-layer data-gradient chain, behind every other slab
+__host__ inline RowMap make_rowmap(int H, const MlpArgs &a, int64_t n_tiles, bool slab, bool chain) {
     RowMap m;
-    m.lay = make_layout(H, L, enc, in_dim, K0_pad, out);
+    const int L = a.n_layers;
+    m.lay = make_layout(H, L, a.enc, a.in_dim, a.K0_pad, a.out_dim);
     m.slab = slab; m.H = H; m.L = L; m.sl = n_tiles * H;
     m.rows_total = slab ? H : m.lay.total;
     m.e_off = 0; m.n_slabs = 0; m.gc_off = 0;
@@ -1121,269 +1134,315 @@ __host__ inline RowMap make_rowmap(int H, int L, int enc, int in_dim, int K0_pad
         // the cross-layer data-gradient chain (mlp_fused_f2.hip) writes every layer's gradient once and the weight-gradient launches read
         // them afterwards: one slab per hidden layer instead of the two ping-pong buffers
         m.gc_off = (int64_t)m.n_slabs * m.sl;
-        m.n_slabs += L - 1;
+        if (chain) m.n_slabs += L - 1;
     }
     return m;
 }
-// rows of a training workspace (without its tail): room for either layout (a backward pass without a stashed forward runs tile-major)
-__host__ inline int64_t ws_rows(int H, int L, int enc, int in_dim, int K0_pad, int out, int64_t n_tiles) {
-    const int64_t tm = make_rowmap(H, L, enc, in_dim, K0_pad, out, n_tiles, false).total_rows(n_tiles);
-    if (!slab_eligible(H, L, enc, in_dim, K0_pad, out)) return tm;
-    return std::max(tm, make_rowmap(H, L, enc, in_dim, K0_pad, out, n_tiles, true).total_rows(n_tiles));
+
+// The training workspace: rows, the tail (WS_TAIL_BYTES), and for cross_layer stacks the packed weight stream.  tn_mlp_fwd_stash and
+// tn_mlp_bwd of one step must agree on it -- the f16x2 weight gradient reads the maxima the forward left in the tail -- so it depends
+// on the shape, the encoding, the arithmetic and TN_MLP_LAYERWISE only.
+struct Workspace {
+    RowMap rm;              // what a stashing forward leaves: slab layout for input_rows stacks, else tile-major
+    int64_t rows;           // rows in front of the tail: room for either layout (an unstashed backward runs tile-major)
+    int64_t pack_off;       // byte offset of the packed weight stream (cross_layer)
+    int64_t bytes;
+};
+__host__ inline Workspace workspace(int H, const MlpArgs &a, int64_t n_tiles) {
+    Workspace w;
+    w.rm = make_rowmap(H, a, n_tiles, input_rows(H, a), cross_layer(H, a));
+    w.rows = std::max<int64_t>(n_tiles * w.rm.lay.total, w.rm.total_rows(n_tiles));
+    w.pack_off = fused_pack_offset(w.rows);
+    w.bytes = cross_layer(H, a) ? w.pack_off + fused_pack_bytes(H, a.n_layers) : w.rows * 32 * (int64_t)sizeof(float) + WS_TAIL_BYTES;
+    return w;
 }
 
-template <int H>
-int run_fwd_only(const MlpArgs &a, const float *x, const float *aux, int64_t n, float *y, float *stash, hipStream_t s, bool inference = false)
+enum class Pass { INFER_FWD, TRAIN_FWD, BWD };
+enum class Fwd { GENERAL, LAYERS, FUSED };          // general-shape kernel / one launch per layer / one persistent launch (mlp_fused_f2.hip)
+enum class First { ENC_F2, ENC_LDS, STASH };        // Fwd::LAYERS' first layer: enc_rows_kernel + fwd_first_f2 / fwd_lds, or fwd_stash_kernel
+enum class GradY { ROWS, OUT_GRAD, RECOMPUTE };     // d loss / d y: rows from the consumer (TN_MLP_GRAD_Y_ROWS), from the stash, or a forward
+enum class Wgrad { F2, B3, LDS, ROWS, TILES2, TILES8 };
+enum class Dgrad { NONE, F2, B3, WREG, LDS, GENERAL, FIRST, FIRST_GENERAL };
+// (the general-shape kinds -- First::STASH, Fwd::GENERAL, Wgrad::TILES8, Dgrad::GENERAL / FIRST_GENERAL -- say so once on a width-128 /
+//  256 stack: tn::warn_once ids 0 - 4)
+
+struct LayerStep {          // backward of layer l: its kinds and their arguments (run_bwd adds the gradient and tail pointers)
+    Wgrad wgrad;
+    Dgrad dgrad;            // Dgrad::F2 launches before the weight gradient: it reports the largest |gradient| that one scales by
+    WgradArgs w;
+    DgradArgs d;
+    int max_a, max_g;       // f16x2 tail slots of the largest |input| / |gradient| of the layer, -1: none
+};
+
+struct Plan {
+    Pass pass;
+    Workspace ws;
+    RowMap rm;              // the rows this pass addresses
+    // forward
+    Fwd fwd;
+    First first;
+    int rows_total, first_kp, n_run;    // rows per tile; input rows of the first layer; layers evaluated (TN_MLP_SKIP_LAST: L - 1)
+    int64_t off_e, off_out[TN_MLP_MAX_LAYERS], off_bits[TN_MLP_MAX_LAYERS];     // layer l reads off_out[l - 1]
+    int64_t pack_off;       // Fwd::FUSED: byte offset of the packed weight stream
+    bool tail;              // f16x2 training forward: clears the tail and reports the layers' input maxima to it
+    bool no_y;              // the f16x2 forms leave y as workspace rows only (TN_MLP_ROWS_ONLY, TN_MLP_SKIP_LAST)
+    // backward
+    GradY grad_y;
+    bool chain;             // the data gradients of layers top .. 1 in one launch (mlp_fused_f2.hip)
+    int top;                // highest layer the backward walks (TN_MLP_SKIP_LAST: L - 2)
+    LayerStep step[TN_MLP_MAX_LAYERS];
+};
+
+int make_plan(const MlpArgs &a, int H, int64_t n, Pass pass, Plan &p, bool stashed = false, bool gy_rows = false, bool want_gx = false)
 {
+    const int L = a.n_layers, out = a.out_dim;
     const int64_t n_tiles = (n + 31) / 32;
-    constexpr int WPB = H <= 64 ? 8 : 4;
-    const int64_t blocks = std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * 2);
-    if constexpr (H >= 128) {
-        const int L = a.n_layers, out = a.out_dim;
-        if (layer_kernel_path(H, L, out)) {       // first layer, then one launch per layer with W in LDS
-            const RowMap rm = make_rowmap(H, L, a.enc, a.in_dim, a.K0_pad, out, n_tiles, !inference && slab_eligible(H, L, a.enc, a.in_dim, a.K0_pad, out));
-            const Layout &lay = rm.lay;
-            const int total = inference ? infer_rows_total(H, lay) : rm.rows_total;
-            const int64_t offE = inference ? 2 * H : rm.offE();
-            auto off_in = [&](int l) -> int64_t { return inference ? ((l - 1) & 1) * H : rm.offH(l - 1); };
-            auto off_out = [&](int l) -> int64_t { return inference ? (l & 1) * H : (l + 1 < L ? rm.offH(l) : rm.offGA()); };
-            auto off_bits = [&](int l) -> int64_t { return (inference || l + 1 >= L) ? -1 : rm.offM(l); };      // activation l = output of layer l
-            float *tail = (a.f2 && !inference && L <= 16) ? ws_tail(stash, ws_rows(H, L, a.enc, a.in_dim, a.K0_pad, out, n_tiles)) : nullptr;
-            if (tail) {
-                hipError_t me = hipMemsetAsync(tail, 0, WS_TAIL_BYTES, s);
-                if (me != hipSuccess) { tn::set_error("mlp_fwd(f16x2): cannot clear the workspace tail: %s", hipGetErrorString(me)); return (int)me; }
-            }
-            const bool plain = plain_x_rows(H, L, a.enc, a.K0_pad, out) && lay.rowsE == 64;
-            if (inference && !a.layerwise && fused_fwd_ok(H, a) && ((a.enc == TN_ENC_POSENC && a.K0_pad <= 64) || plain)) {
-                // round 6: the whole stack as ONE persistent launch (mlp_fused_f2.hip) -- the workspace holds the encoded input rows (64 per
-                // tile, contiguous over the tiles) and, behind the layer-wise form's area, the packed weight stream
-                enc_rows_kernel<<<dim3((unsigned)std::min<int64_t>((n_tiles + 3) / 4, 256 * 8)), dim3(256), 0, s>>>(a, x, n, stash, 64, 0, plain ? 64 : a.K0_pad);
-                if (int rc = tn::check_launch("enc_rows_kernel")) return rc;
-                if (!plain && a.K0_pad < 64) {               // rows K0_pad .. 63 of every tile are operands too (zero weights, but 0 x NaN = NaN)
-                    hipError_t me = hipMemset2DAsync(stash + (size_t)a.K0_pad * 32, 64 * 128, 0, (size_t)(64 - a.K0_pad) * 128, (size_t)n_tiles, s);
-                    if (me != hipSuccess) { tn::set_error("mlp_fwd(fused): cannot clear the padding rows: %s", hipGetErrorString(me)); return (int)me; }
-                }
-                void *pack = reinterpret_cast<unsigned char *>(stash) + infer_ws_rows_bytes(H, lay, n_tiles);
-                return launch_fused_fwd_f2(H, a, n, stash, y, pack, s);
-            }
-            if (!inference && !a.layerwise && rm.slab && a.f2 && tail && lay.rowsE == 64 && fused_fwd_ok(H, a) &&
-                ((a.enc == TN_ENC_POSENC && a.K0_pad == 64) || plain) && (!a.skip_last || out == H)) {
-                // round 6: the training forward as ONE persistent launch (mlp_fused_f2.hip): activations stay in registers across the layers and
-                // reach the workspace as the rows, bit rows and maxima the layer-wise backward reads -- written once, never read back here
-                enc_rows_kernel<<<dim3((unsigned)std::min<int64_t>((n_tiles + 3) / 4, 256 * 8)), dim3(256), 0, s>>>(a, x, n, stash, total, offE, 64);
-                if (int rc = tn::check_launch("enc_rows_kernel")) return rc;
-                FusedStash sp;
-                sp.rows = stash; sp.rows_total = total; sp.off_e = offE; sp.n_run = L - (a.skip_last ? 1 : 0); sp.tail = tail;
-                for (int l = 0; l < TN_MLP_MAX_LAYERS; ++l) { sp.off_out[l] = 0; sp.off_bits[l] = 0; }
-                for (int l = 0; l < sp.n_run; ++l) { sp.off_out[l] = off_out(l); sp.off_bits[l] = std::max<int64_t>(off_bits(l), 0); }
-                float *y_f = (a.skip_last || (a.rows_only && out == H && a.out_act == TN_ACT_NONE)) ? nullptr : y;
-                return launch_fused_fwd_f2(H, a, n, stash, y_f, fused_pack_area(stash, ws_rows(H, L, a.enc, a.in_dim, a.K0_pad, out, n_tiles)), s, &sp);
-            }
-            if ((a.enc == TN_ENC_POSENC && a.K0_pad <= 64) || plain) {      // (encoded) inputs as rows, then the first layer like any other
-                enc_rows_kernel<<<dim3((unsigned)std::min<int64_t>((n_tiles + 3) / 4, 256 * 8)), dim3(256), 0, s>>>(a, x, n, stash, total, offE,
-                                                                                                                  plain ? 64 : a.K0_pad);
-                if (int rc = tn::check_launch("enc_rows_kernel")) return rc;
-                FwdLayerArgs f;
-                f.W = a.W[0]; f.B = a.B[0]; f.N = a.N[0]; f.K = a.K0; f.Kp = plain ? 64 : a.K0_pad; f.rows_total = total;
-                f.off_in = offE; f.off_out = inference ? 0 : rm.offH(0); f.out_act = a.out_act; f.off_bits = off_bits(0);
-                if (a.f2) { if (int rc = launch_fwd_first_f2(H, f, n, stash, s)) return rc; }
-                else if (int rc = launch_fwd_lds<H, 2, H / 32>(f, n, stash, y, s)) return rc;
-            } else {
-                if (inference) return tn::fail(TN_E_CONFIG, "tn_mlp_fwd_ws: the layer-by-layer inference forward needs positional-encoding inputs");
-                tn::warn_once(0, "mlp forward: the first layer of this width-%d stack (encoding %d, %d inputs) runs on the general-shape kernel "
-                              "(fast forms: positional encoding with <= 64 slots, or <= 64 plain inputs)", H, a.enc, a.in_dim);
-                fwd_stash_kernel<H, WPB, true, true><<<dim3((unsigned)std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * 4)), dim3(WPB * 64), 0, s>>>(
-                    a, x, aux, nullptr, n, stash, y);
-                if (int rc = tn::check_launch("fwd_stash_kernel(first layer)")) return rc;
-            }
-            if (a.skip_last && (inference || !rm.slab || !a.f2 || out != H))
-                return tn::fail(TN_E_CONFIG, "tn_mlp_fwd_stash: TN_MLP_SKIP_LAST needs the f16x2 training forward of a slab-layout stack whose output is as wide as its hidden layers");
-            for (int l = 1; l < L - (a.skip_last ? 1 : 0); ++l) {       // (TN_MLP_SKIP_LAST: the caller merged the last layer into its consumers)
-                FwdLayerArgs f;
-                f.W = a.W[l]; f.B = a.B[l]; f.N = a.N[l]; f.K = a.K[l]; f.Kp = a.K[l]; f.rows_total = total;
-                f.off_in = off_in(l); f.off_out = off_out(l); f.out_act = a.out_act; f.off_bits = off_bits(l);
-                f.max_in = tail ? tail + l : nullptr;
-                // hidden layers (K == N == H) and the output layer (K == H, N <= H): weights in registers
-                int rc;
-                // TN_MLP_ROWS_ONLY: the last layer leaves its output as workspace rows only (out == H, no output activation: the
-                // rows ARE y -- the conditions of tn_mlp_rows_view)
-                float *y_l = (l + 1 == L && a.rows_only && !inference && a.f2 && out == H && a.out_act == TN_ACT_NONE) ? nullptr : y;
-                if (a.f2) rc = launch_fwd_f2(H, l + 1 == L, f, n, stash, y_l, s);      // fp16 matrix cores, two-term splits, scaled
-                else if (a.b3) rc = launch_fwd_b3(H, l + 1 == L, f, n, stash, y, s);   // bf16 matrix cores, exact 3-way splits
-                else rc = l + 1 < L ? launch_fwd_wreg<H, false>(f, n, stash, y, s) : launch_fwd_wreg<H, true>(f, n, stash, y, s);
-                if (rc) return rc;
-            }
-            return TN_OK;
+    const bool train = pass != Pass::INFER_FWD;
+    p.pass = pass;
+    p.ws = workspace(H, a, n_tiles);
+    // (the slab layout is what the stashing forward of the same configuration left behind)
+    p.rm = pass == Pass::TRAIN_FWD || stashed ? p.ws.rm : make_rowmap(H, a, n_tiles, false, false);
+    const RowMap &rm = p.rm;
+    if (pass != Pass::BWD) {
+        TN_REQUIRE(!a.skip_last || (train && skip_last_ok(H, a)), TN_E_CONFIG,
+                   "tn_mlp_fwd_stash: TN_MLP_SKIP_LAST needs the f16x2 training forward of a slab-layout stack whose output is as wide as its hidden layers");
+        TN_REQUIRE(train || input_rows(H, a), TN_E_CONFIG, "tn_mlp_fwd_ws: configuration without a layer-by-layer inference forward");
+        p.fwd = !layer_kernel_path(H, a) ? Fwd::GENERAL : fused_fwd(H, a) && (!train || rm.lay.rowsE == 64) ? Fwd::FUSED : Fwd::LAYERS;
+        p.first = !input_rows(H, a) ? First::STASH : a.f2 ? First::ENC_F2 : First::ENC_LDS;
+        p.first_kp = a.enc == TN_ENC_NONE ? 64 : a.K0_pad;
+        p.n_run = L - (a.skip_last ? 1 : 0);
+        p.tail = train && a.f2 && p.fwd != Fwd::GENERAL;
+        p.no_y = train && a.f2 && out == H && a.out_act == TN_ACT_NONE && (a.rows_only || a.skip_last);
+        p.pack_off = train ? p.ws.pack_off : infer_ws_rows_bytes(H, rm.lay, n_tiles);
+        if (train) {
+            p.rows_total = rm.rows_total; p.off_e = rm.offE();
+        } else if (p.fwd == Fwd::FUSED) {        // 64 encoded-input rows per tile, contiguous over the tiles
+            p.rows_total = 64; p.off_e = 0;
+        } else {
+            p.rows_total = infer_rows_total(H, rm.lay); p.off_e = 2 * H;
+        }
+        for (int l = 0; l < TN_MLP_MAX_LAYERS; ++l) {
+            p.off_out[l] = !train ? (l & 1) * H : l + 1 < L ? rm.offH(l) : rm.offGA();
+            p.off_bits[l] = train && l + 1 < L ? rm.offM(l) : -1;
+        }
+        return TN_OK;
+    }
+    if (a.skip_last) TN_REQUIRE(gy_rows && stashed && skip_last_ok(H, a), TN_E_CONFIG, "tn_mlp_bwd: TN_MLP_SKIP_LAST needs TN_MLP_STASHED | TN_MLP_GRAD_Y_ROWS on the f16x2 slab-layout stack");
+    // TN_MLP_GRAD_Y_ROWS: the consumers of y (the heads' data-gradient chains) have written d loss / d y as rows into buffer B
+    // (tn_mlp_rows_view): nothing to transpose, the walk starts from B and ping-pongs into A
+    if (gy_rows) TN_REQUIRE(stashed && a.out_act == TN_ACT_NONE && (out & 31) == 0, TN_E_CONFIG,
+                            "tn_mlp_bwd: TN_MLP_GRAD_Y_ROWS needs TN_MLP_STASHED, no output activation and out_dim % 32 == 0");
+    p.grad_y = gy_rows ? GradY::ROWS : stashed ? GradY::OUT_GRAD : GradY::RECOMPUTE;
+    p.chain = stashed && cross_layer(H, a);
+    p.top = L - 1 - (a.skip_last ? 1 : 0);
+    // ReLU bit rows exist for every activation the training forward of the layer-kernel path wrote
+    const bool bits = stashed && layer_kernel_path(H, a);
+    int64_t cur = gy_rows ? rm.offGB() : rm.offGA(), nxt = gy_rows ? rm.offGA() : rm.offGB();
+    for (int l = p.top; l >= 0; --l) {
+        LayerStep &st = p.step[l];
+        WgradArgs &w = st.w;
+        DgradArgs &d = st.d;
+        w.N = d.N = a.N[l]; w.K = d.K = a.K[l]; w.K_pad = l == 0 ? a.K0_pad : a.K[l]; w.rows_total = d.rows_total = rm.rows_total;
+        w.off_g = d.off_gin = p.chain && l < p.top ? rm.offGC(l) : cur;         // d loss / d (pre-activation of layer l)
+        w.off_a = d.off_mask = l > 0 ? rm.offH(l - 1) : 0;                       // the layer's input activation
+        w.off_e = rm.offE(); d.off_gout = nxt; d.off_bits = bits && l > 0 ? rm.offM(l - 1) : -1;
+        w.first = l == 0; w.enc = d.enc = a.enc; w.in_dim = d.in_dim = a.in_dim; w.n_freqs = d.n_freqs = a.n_freqs; w.xs = rm.lay.xs;
+        d.W = a.W[l]; d.accum_gx = a.accum_gx;
+        const bool square = H >= 128 && l > 0 && a.N[l] == H;        // (K = H for every l > 0)
+        // f16x2: the layer's data gradient first -- it reports the largest |gradient| of the rows both kernels read -- then the weight
+        // gradient with that scale and the one the forward pass left for the layer's input rows
+        const bool f2 = square && a.f2 && bits;
+        st.max_a = f2 ? l : -1;
+        st.max_g = f2 ? 16 + l : -1;
+        if (f2) st.wgrad = Wgrad::F2;
+        else if (square) st.wgrad = a.b3 ? Wgrad::B3 : Wgrad::LDS;
+        // first layer on input rows: plain inputs the training forward staged as 64 rows (Cobafa's 36 features), or positional-encoding
+        // slots of a width-256 stack (<= 64, all of them E rows of the workspace) -- the row-operand kernel of mlp_wgrad_rows.hip
+        else if (l == 0 && H >= 128 && ((stashed && plain_x_rows(H, L, a.enc, a.K0_pad, out)) || (H == 256 && a.enc == TN_ENC_POSENC && a.K0_pad == 64)))
+            st.wgrad = Wgrad::ROWS;
+        else {
+            const int tiles = ((a.N[l] + 31) / 32) * (((l == 0 ? a.K0_pad : a.K[l]) + 31) / 32);
+            if (tiles > 64) return tn::fail(TN_E_CONFIG, "mlp_bwd: layer too large for the wgrad tiling");
+            st.wgrad = tiles <= 16 ? Wgrad::TILES2 : Wgrad::TILES8;
+        }
+        if (l > 0) {
+            if (f2) st.dgrad = p.chain ? Dgrad::NONE : Dgrad::F2;          // (chain: its launch writes the rows and the maximum)
+            else if (square) st.dgrad = a.b3 && bits ? Dgrad::B3 : Dgrad::WREG;
+            else if (H >= 128 && a.N[l] <= H) st.dgrad = Dgrad::LDS;      // weights of this layer's column group in LDS
+            else st.dgrad = Dgrad::GENERAL;
+            std::swap(cur, nxt);
+        } else if (want_gx && a.enc != TN_ENC_POSENC) {                     // d loss / d x of a narrow plain input: W_0^T in LDS
+            st.dgrad = H >= 128 && a.enc == TN_ENC_NONE && a.in_dim <= 64 ? Dgrad::FIRST : Dgrad::FIRST_GENERAL;
+        } else {
+            st.dgrad = Dgrad::NONE;
         }
     }
-    if (inference) return tn::fail(TN_E_CONFIG, "tn_mlp_fwd_ws: configuration without a layer-by-layer inference forward");
-    if (H >= 128) tn::warn_once(1, "mlp forward: this width-%d stack (%d layers, %d outputs) is outside the layer-by-layer kernels and runs on "
-                                   "the general-shape kernel", H, a.n_layers, a.out_dim);
-    fwd_stash_kernel<H, WPB, true><<<dim3((unsigned)blocks), dim3(WPB * 64), 0, s>>>(a, x, aux, nullptr, n, stash, y);
-    return tn::check_launch("fwd_stash_kernel(forward)");
+    return TN_OK;
 }
 
 template <int H>
-int run_layers(const MlpArgs &a, const float *x, const float *aux, const float *gy, int64_t n, float *const *gw,
-               float *const *gb, float *gx, float *stash, hipStream_t s, bool stashed = false, bool gy_rows = false)
+int run_fwd(const Plan &p, const MlpArgs &a, const float *x, const float *aux, int64_t n, float *y, float *stash, hipStream_t s)
 {
-    const int L = a.n_layers;
     const int64_t n_tiles = (n + 31) / 32;
-    // (the slab layout is what the stashing forward of the same configuration left behind, run_fwd_only)
-    const RowMap rm = make_rowmap(H, L, a.enc, a.in_dim, a.K0_pad, a.out_dim, n_tiles, stashed && slab_eligible(H, L, a.enc, a.in_dim, a.K0_pad, a.out_dim));
-    const Layout &lay = rm.lay;
-    const int64_t tail_rows = ws_rows(H, L, a.enc, a.in_dim, a.K0_pad, a.out_dim, n_tiles);
     constexpr int WPB = H <= 64 ? 8 : 4;
-    if (a.skip_last) TN_REQUIRE(gy_rows && stashed && rm.slab && a.f2, TN_E_CONFIG, "tn_mlp_bwd: TN_MLP_SKIP_LAST needs TN_MLP_STASHED | TN_MLP_GRAD_Y_ROWS on the f16x2 slab-layout stack");
-    if (gy_rows) {
-        // TN_MLP_GRAD_Y_ROWS: the consumers of y (the heads' data-gradient chains) have written d loss / d y as rows into
-        // buffer B (tn_mlp_rows_view): nothing to transpose, the walk below starts from B and ping-pongs into A
-        TN_REQUIRE(stashed && a.out_act == TN_ACT_NONE && (a.out_dim & 31) == 0, TN_E_CONFIG,
-                   "tn_mlp_bwd: TN_MLP_GRAD_Y_ROWS needs TN_MLP_STASHED, no output activation and out_dim % 32 == 0");
-    } else if (stashed) {        // activations and the last pre-activation are in the workspace already (tn_mlp_fwd_stash)
+    if (p.fwd == Fwd::GENERAL) {
+        if (H >= 128) tn::warn_once(1, "mlp forward: this width-%d stack (%d layers, %d outputs) is outside the layer-by-layer kernels and runs on "
+                                       "the general-shape kernel", H, a.n_layers, a.out_dim);
+        fwd_stash_kernel<H, WPB, true><<<dim3((unsigned)std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * 2)), dim3(WPB * 64), 0, s>>>(
+            a, x, aux, nullptr, n, stash, y);
+        return tn::check_launch("fwd_stash_kernel(forward)");
+    }
+    if constexpr (H >= 128) {
+        float *tail = p.tail ? ws_tail(stash, p.ws.rows) : nullptr;
+        if (tail) {
+            hipError_t me = hipMemsetAsync(tail, 0, WS_TAIL_BYTES, s);
+            if (me != hipSuccess) { tn::set_error("mlp_fwd(f16x2): cannot clear the workspace tail: %s", hipGetErrorString(me)); return (int)me; }
+        }
+        if (p.fwd == Fwd::FUSED || p.first != First::STASH) {          // (encoded) inputs as rows
+            enc_rows_kernel<<<dim3((unsigned)std::min<int64_t>((n_tiles + 3) / 4, 256 * 8)), dim3(256), 0, s>>>(a, x, n, stash, p.rows_total, p.off_e,
+                                                                                                              p.first_kp);
+            if (int rc = tn::check_launch("enc_rows_kernel")) return rc;
+        }
+        if (p.fwd == Fwd::FUSED) {
+            // round 6: the whole stack as ONE persistent launch (mlp_fused_f2.hip); in training, activations stay in registers across the
+            // layers and reach the workspace as the rows, bit rows and maxima the layer-wise backward reads -- written once, never read back
+            void *pack = reinterpret_cast<unsigned char *>(stash) + p.pack_off;
+            float *y_f = p.no_y ? nullptr : y;
+            if (p.pass == Pass::INFER_FWD) {
+                if (p.first_kp < 64) {               // rows K0_pad .. 63 of every tile are operands too (zero weights, but 0 x NaN = NaN)
+                    hipError_t me = hipMemset2DAsync(stash + (size_t)p.first_kp * 32, (size_t)p.rows_total * 128, 0, (size_t)(64 - p.first_kp) * 128,
+                                                     (size_t)n_tiles, s);
+                    if (me != hipSuccess) { tn::set_error("mlp_fwd(fused): cannot clear the padding rows: %s", hipGetErrorString(me)); return (int)me; }
+                }
+                return launch_fused_fwd_f2(H, a, n, stash, y_f, pack, s);
+            }
+            FusedStash sp;
+            sp.rows = stash; sp.rows_total = p.rows_total; sp.off_e = p.off_e; sp.n_run = p.n_run; sp.tail = tail;
+            for (int l = 0; l < TN_MLP_MAX_LAYERS; ++l) { sp.off_out[l] = 0; sp.off_bits[l] = 0; }
+            for (int l = 0; l < p.n_run; ++l) { sp.off_out[l] = p.off_out[l]; sp.off_bits[l] = std::max<int64_t>(p.off_bits[l], 0); }
+            return launch_fused_fwd_f2(H, a, n, stash, y_f, pack, s, &sp);
+        }
+        if (p.first == First::STASH) {
+            tn::warn_once(0, "mlp forward: the first layer of this width-%d stack (encoding %d, %d inputs) runs on the general-shape kernel "
+                          "(fast forms: positional encoding with <= 64 slots, or <= 64 plain inputs)", H, a.enc, a.in_dim);
+            fwd_stash_kernel<H, WPB, true, true><<<dim3((unsigned)std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * 4)), dim3(WPB * 64), 0, s>>>(
+                a, x, aux, nullptr, n, stash, y);
+            if (int rc = tn::check_launch("fwd_stash_kernel(first layer)")) return rc;
+        } else {
+            FwdLayerArgs f;
+            f.W = a.W[0]; f.B = a.B[0]; f.N = a.N[0]; f.K = a.K0; f.Kp = p.first_kp; f.rows_total = p.rows_total;
+            f.off_in = p.off_e; f.off_out = p.off_out[0]; f.out_act = a.out_act; f.off_bits = p.off_bits[0];
+            if (p.first == First::ENC_F2) { if (int rc = launch_fwd_first_f2(H, f, n, stash, s)) return rc; }
+            else if (int rc = launch_fwd_lds<H, 2, H / 32>(f, n, stash, y, s)) return rc;
+        }
+        for (int l = 1; l < p.n_run; ++l) {
+            FwdLayerArgs f;
+            f.W = a.W[l]; f.B = a.B[l]; f.N = a.N[l]; f.K = a.K[l]; f.Kp = a.K[l]; f.rows_total = p.rows_total;
+            f.off_in = p.off_out[l - 1]; f.off_out = p.off_out[l]; f.out_act = a.out_act; f.off_bits = p.off_bits[l];
+            f.max_in = tail ? tail + l : nullptr;
+            // hidden layers (K == N == H) and the output layer (K == H, N <= H): weights in registers
+            const bool last = l + 1 == a.n_layers;
+            int rc;
+            if (a.f2) rc = launch_fwd_f2(H, last, f, n, stash, last && p.no_y ? nullptr : y, s);     // fp16 matrix cores, two-term splits, scaled
+            else if (a.b3) rc = launch_fwd_b3(H, last, f, n, stash, y, s);                          // bf16 matrix cores, exact 3-way splits
+            else rc = last ? launch_fwd_wreg<H, true>(f, n, stash, y, s) : launch_fwd_wreg<H, false>(f, n, stash, y, s);
+            if (rc) return rc;
+        }
+    }
+    return TN_OK;
+}
+
+template <int H>
+int run_bwd(const Plan &p, const MlpArgs &a, const float *x, const float *aux, const float *gy, int64_t n, float *const *gw,
+            float *const *gb, float *gx, float *stash, hipStream_t s)
+{
+    const RowMap &rm = p.rm;
+    const int64_t n_tiles = (n + 31) / 32;
+    constexpr int WPB = H <= 64 ? 8 : 4;
+    float *tail = ws_tail(stash, p.ws.rows);
+    if (p.grad_y == GradY::OUT_GRAD) {        // activations and the last pre-activation are in the workspace already (tn_mlp_fwd_stash)
         out_grad_kernel<<<dim3((unsigned)std::min<int64_t>(n_tiles, 256 * 8)), dim3(256), 0, s>>>(gy, n, a.out_dim, a.out_act, rm.rows_total,
                                                                                          rm.offGA(), stash);
         if (int rc = tn::check_launch("out_grad_kernel")) return rc;
-    } else {
-        const int64_t blocks = std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * 2);
-        fwd_stash_kernel<H, WPB><<<dim3((unsigned)blocks), dim3(WPB * 64), 0, s>>>(a, x, aux, gy, n, stash);
+    } else if (p.grad_y == GradY::RECOMPUTE) {
+        fwd_stash_kernel<H, WPB><<<dim3((unsigned)std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * 2)), dim3(WPB * 64), 0, s>>>(a, x, aux, gy, n, stash);
         if (int rc = tn::check_launch("fwd_stash_kernel")) return rc;
     }
-    const int64_t offE = rm.offE(), offGA = rm.offGA(), offGB = rm.offGB();
-    int64_t cur = gy_rows ? offGB : offGA, nxt = gy_rows ? offGA : offGB;
-    const int top = L - 1 - (a.skip_last ? 1 : 0);
-    // round 6: every data gradient of the stack in ONE persistent launch (mlp_fused_f2.hip fused_chain_kernel): the gradients stay in
-    // registers between the layers and reach the workspace once, as the rows the weight-gradient launches below read
-    bool chain = false;
-    if constexpr (H == 128 || H == 256) {
-        bool square = top >= 1;
-        for (int l = 1; l <= top; ++l) square = square && a.N[l] == H && a.K[l] == H;
-        if (stashed && rm.slab && a.f2 && !a.layerwise && square && L <= 16 && layer_kernel_path(H, L, a.out_dim)) {
-            FusedChain fc;
-            fc.rows = stash; fc.rows_total = rm.rows_total; fc.off_in = cur; fc.tail = ws_tail(stash, tail_rows);
-            for (int i = 0; i < TN_MLP_MAX_LAYERS; ++i) { fc.off_out[i] = 0; fc.off_bits[i] = 0; fc.tail_idx[i] = -1; }
-            for (int i = 0; i < top; ++i) {
-                const int l = top - i;
-                fc.off_out[i] = rm.offGC(l - 1); fc.off_bits[i] = rm.offM(l - 1); fc.tail_idx[i] = 16 + l;
-            }
-            if (int rc = launch_fused_chain_f2(H, a, top, n, fused_pack_area(stash, tail_rows), s, &fc)) return rc;
-            chain = true;
+    if (p.chain) {
+        // round 6: every data gradient of the stack in ONE persistent launch (mlp_fused_f2.hip fused_chain_kernel): the gradients stay in
+        // registers between the layers and reach the workspace once, as the rows the weight-gradient launches below read
+        FusedChain fc;
+        fc.rows = stash; fc.rows_total = rm.rows_total; fc.off_in = p.step[p.top].w.off_g; fc.tail = tail;
+        for (int i = 0; i < TN_MLP_MAX_LAYERS; ++i) { fc.off_out[i] = 0; fc.off_bits[i] = 0; fc.tail_idx[i] = -1; }
+        for (int i = 0; i < p.top; ++i) {
+            const LayerStep &st = p.step[p.top - i];
+            fc.off_out[i] = p.step[p.top - i - 1].w.off_g; fc.off_bits[i] = st.d.off_bits; fc.tail_idx[i] = st.max_g;
         }
+        if (int rc = launch_fused_chain_f2(H, a, p.top, n, reinterpret_cast<unsigned char *>(stash) + p.ws.pack_off, s, &fc)) return rc;
     }
-    const int64_t top_off = cur;
-    auto g_rows = [&](int l) -> int64_t { return chain ? (l == top ? top_off : rm.offGC(l)) : cur; };       // d loss / d (pre-activation of layer l)
-    // (TN_MLP_SKIP_LAST: buffer B holds d loss / d (pre-activation of layer L - 2) -- the walk starts one layer lower)
-    for (int l = top; l >= 0; --l) {
-        WgradArgs w;
-        w.gW = gw[l]; w.gB = gb[l]; w.N = a.N[l]; w.K = a.K[l]; w.K_pad = l == 0 ? a.K0_pad : a.K[l];
-        w.rows_total = rm.rows_total; w.off_g = g_rows(l); w.off_a = l > 0 ? rm.offH(l - 1) : 0; w.off_e = offE;
-        w.first = l == 0; w.enc = a.enc; w.in_dim = a.in_dim; w.n_freqs = a.n_freqs; w.xs = lay.xs;
-        const int tiles = ((w.N + 31) / 32) * ((w.K_pad + 31) / 32);
+    for (int l = p.top; l >= 0; --l) {
+        const LayerStep &st = p.step[l];
+        WgradArgs w = st.w;
+        w.gW = gw[l]; w.gB = gb[l];
+        if (st.max_g >= 0) { w.g_max = tail + st.max_g; w.a_max = tail + st.max_a; }
+        DgradArgs d = st.d;
+        if (st.dgrad == Dgrad::F2) {
+            d.max_in = tail + st.max_g;
+            if (int rc = launch_dgrad_f2(H, d, n, stash, s)) return rc;
+        }
         const int64_t wblocks = std::min<int64_t>(n_tiles, 256 * 2);
-        bool staged = false, dgrad_done = false;
-        if constexpr (H == 256 || H == 128) {
-            // f16x2: the layer's data gradient first -- it reports the largest |gradient| of the rows both kernels read -- then the
-            // weight gradient with that scale and the one the forward pass left for the layer's input rows
-            if (!w.first && w.N == H && w.K == H && a.f2 && stashed && layer_kernel_path(H, L, a.out_dim) && L <= 16) {
-                float *tail = ws_tail(stash, tail_rows);
-                DgradArgs d;
-                d.W = a.W[l]; d.N = a.N[l]; d.K = a.K[l]; d.rows_total = rm.rows_total;
-                d.off_gin = cur; d.off_gout = nxt; d.off_mask = rm.offH(l - 1);
-                d.off_bits = rm.offM(l - 1);
-                d.enc = a.enc; d.in_dim = a.in_dim; d.n_freqs = a.n_freqs; d.accum_gx = a.accum_gx;
-                d.max_in = tail + 16 + l;
-                if (!chain) { if (int rc = launch_dgrad_f2(H, d, n, stash, s)) return rc; }       // (chain: its launch has written the rows and the maximum)
-                dgrad_done = true;
-                w.g_max = tail + 16 + l; w.a_max = tail + l;
-                if (int rc = launch_wgrad_f2(H, w, n, stash, s)) return rc;
-                staged = true;
-            }
-        }
-        if constexpr (H == 256 || H == 128) {
-            if (!staged && !w.first && w.N == H && w.K == H) {
-                if (a.b3) { if (int rc = launch_wgrad_b3(H, w, n, stash, s)) return rc; }
-                else if (int rc = launch_wgrad_lds<H, 2, H == 256 ? 4 : 1>(w, n, stash, s)) return rc;
-                staged = true;
-            }
-        }
-        if constexpr (H == 256 || H == 128) {
-            // plain inputs staged as 64 rows by the training forward (Cobafa's 36 features): same kernel, 128 x 64 / 256 x 64
-            if (!staged && w.first && stashed && lay.rowsE == 64 && plain_x_rows(H, L, a.enc, a.K0_pad, a.out_dim) && w.N == H) {
-                if (int rc = tn_mlp_wgrad_rows(stash + g_rows(l) * 32, (int64_t)rm.rows_total * 32, H, stash + offE * 32,
-                                               (int64_t)rm.rows_total * 32, 64, w.gW, w.K, 0, w.K, w.gB, n, s)) return rc;
-                staged = true;
-            }
-        }
-        if constexpr (H == 256) {
-            // first layer of the width-256 stack on positional-encoding inputs (<= 64 slots, all of them E rows of this workspace):
-            // the row-operand kernel of mlp_wgrad_rows.hip (LDS-direct tiles, 2 x 1 accumulator tiles per wave) instead of
-            // per-wave operand loads from L2
-            if (!staged && w.first && lay.xs == 0 && w.K_pad == 64 && w.N == H) {
-                if (int rc = tn_mlp_wgrad_rows(stash + g_rows(l) * 32, (int64_t)rm.rows_total * 32, H, stash + offE * 32,
-                                               (int64_t)rm.rows_total * 32, 64, w.gW, w.K, 0, w.K, w.gB, n, s)) return rc;
-                staged = true;
-            }
-        }
-        if (staged) {}
-        else if (tiles <= 16) wgrad_layer_kernel<2><<<dim3((unsigned)wblocks), dim3(512), 0, s>>>(w, x, n, stash);
-        else if (tiles <= 64) {
+        int rc = TN_OK;
+        switch (st.wgrad) {           // (the kinds that instantiate a kernel per width only occur for H >= 128)
+        case Wgrad::F2: rc = launch_wgrad_f2(H, w, n, stash, s); break;
+        case Wgrad::B3: rc = launch_wgrad_b3(H, w, n, stash, s); break;
+        case Wgrad::LDS: if constexpr (H >= 128) rc = launch_wgrad_lds<H, 2, H == 256 ? 4 : 1>(w, n, stash, s); break;
+        case Wgrad::ROWS:
+            rc = tn_mlp_wgrad_rows(stash + w.off_g * 32, (int64_t)rm.rows_total * 32, H, stash + rm.offE() * 32, (int64_t)rm.rows_total * 32, 64,
+                                   w.gW, w.K, 0, w.K, w.gB, n, s);
+            break;
+        case Wgrad::TILES2:
+            wgrad_layer_kernel<2><<<dim3((unsigned)wblocks), dim3(512), 0, s>>>(w, x, n, stash);
+            rc = tn::check_launch("wgrad_layer_kernel");
+            break;
+        case Wgrad::TILES8:
             if (H >= 128) tn::warn_once(2, "mlp backward: weight gradient of a %d x %d layer on the general-shape kernel (8 tiles per wave, spills)", w.N, w.K);
             wgrad_layer_kernel<8><<<dim3((unsigned)wblocks), dim3(512), 0, s>>>(w, x, n, stash);
+            rc = tn::check_launch("wgrad_layer_kernel");
+            break;
         }
-        else return tn::fail(TN_E_CONFIG, "mlp_bwd: layer too large for the wgrad tiling");
-        if (int rc = tn::check_launch("wgrad_layer_kernel")) return rc;
-
-        DgradArgs d;
-        d.W = a.W[l]; d.N = a.N[l]; d.K = a.K[l]; d.rows_total = rm.rows_total;
-        d.off_gin = g_rows(l); d.off_gout = nxt; d.off_mask = l > 0 ? rm.offH(l - 1) : 0;
-        // ReLU bit rows exist for every activation the training forward of the layer-kernel path wrote (run_fwd_only)
-        const bool bits = stashed && layer_kernel_path(H, L, a.out_dim) && l >= 1;
-        d.off_bits = bits ? rm.offM(l - 1) : -1;
-        d.enc = a.enc; d.in_dim = a.in_dim; d.n_freqs = a.n_freqs; d.accum_gx = a.accum_gx;
+        if (rc) return rc;
         const int64_t blocks = std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * 4);
-        if (l > 0) {
-            bool done = dgrad_done || chain;
+        switch (st.dgrad) {
+        case Dgrad::NONE: case Dgrad::F2: break;
+        case Dgrad::B3: rc = launch_dgrad_b3(H, d, n, stash, s); break;
+        case Dgrad::WREG: if constexpr (H >= 128) rc = launch_dgrad_wreg<H>(d, n, stash, s); break;
+        case Dgrad::LDS:
             if constexpr (H >= 128) {
-                if (done) {}
-                else if (a.K[l] == H && a.N[l] == H) {
-                    if (a.f2 && d.off_bits >= 0) { if (int rc = launch_dgrad_f2(H, d, n, stash, s)) return rc; }
-                    else if (a.b3 && d.off_bits >= 0) { if (int rc = launch_dgrad_b3(H, d, n, stash, s)) return rc; }
-                    else if (int rc = launch_dgrad_wreg<H>(d, n, stash, s)) return rc;
-                    done = true;
-                } else if (a.K[l] == H && a.N[l] <= H) {          // weights of this layer's column group in LDS
-                    constexpr int NKT = 4, WL = 8;
-                    constexpr size_t lds_bytes = (size_t)32 * NKT * (H + 4) * 4;
-                    auto kern = dgrad_lds_kernel<H, NKT, WL>;
-                    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                    if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-                    const int groups = (H / 32) / NKT;
-                    const int per_cu = lds_bytes * 2 <= 160 * 1024 ? 2 : 1;
-                    const int64_t bl = std::min<int64_t>((n_tiles + WL - 1) / WL, (256 * per_cu) / groups);
-                    kern<<<dim3((unsigned)bl, (unsigned)groups), dim3(WL * 64), lds_bytes, s>>>(d, n, stash);
-                    if (int rc = tn::check_launch("dgrad_lds_kernel")) return rc;
-                    done = true;
-                }
+                constexpr int NKT = 4, WL = 8;
+                constexpr size_t lds_bytes = (size_t)32 * NKT * (H + 4) * 4;
+                auto kern = dgrad_lds_kernel<H, NKT, WL>;
+                hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+                if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
+                const int groups = (H / 32) / NKT;
+                const int per_cu = lds_bytes * 2 <= 160 * 1024 ? 2 : 1;
+                const int64_t bl = std::min<int64_t>((n_tiles + WL - 1) / WL, (256 * per_cu) / groups);
+                kern<<<dim3((unsigned)bl, (unsigned)groups), dim3(WL * 64), lds_bytes, s>>>(d, n, stash);
+                rc = tn::check_launch("dgrad_lds_kernel");
             }
-            if (!done) {
-                if (H >= 128) tn::warn_once(3, "mlp backward: data gradient of a %d x %d layer of a width-%d stack on the general-shape kernel", d.N, d.K, H);
-                dgrad_layer_kernel<H, false, WPB><<<dim3((unsigned)blocks), dim3(WPB * 64), 0, s>>>(d, n, stash, nullptr);
-                if (int rc = tn::check_launch("dgrad_layer_kernel")) return rc;
-            }
-            std::swap(cur, nxt);
-        } else if (gx != nullptr && a.enc != TN_ENC_POSENC) {
-            bool done = false;
-            if constexpr (H == 128 || H == 256) {
-                if (a.enc == TN_ENC_NONE && a.in_dim <= 64 && a.N[0] == H) {      // d loss / d x of a narrow plain input: W_0^T in LDS
-                    if (int rc = launch_dgrad_first<H>(d, n, stash, gx, s)) return rc;
-                    done = true;
-                }
-            }
-            if (!done) {
-                if (H >= 128) tn::warn_once(4, "mlp backward: d loss / d x of a width-%d stack with %d inputs (encoding %d) on the general-shape kernel", H, a.in_dim, a.enc);
-                dgrad_layer_kernel<H, true, WPB><<<dim3((unsigned)blocks), dim3(WPB * 64), 0, s>>>(d, n, stash, gx);
-                if (int rc = tn::check_launch("dgrad_layer_kernel(first)")) return rc;
-            }
+            break;
+        case Dgrad::GENERAL:
+            if (H >= 128) tn::warn_once(3, "mlp backward: data gradient of a %d x %d layer of a width-%d stack on the general-shape kernel", d.N, d.K, H);
+            dgrad_layer_kernel<H, false, WPB><<<dim3((unsigned)blocks), dim3(WPB * 64), 0, s>>>(d, n, stash, nullptr);
+            rc = tn::check_launch("dgrad_layer_kernel");
+            break;
+        case Dgrad::FIRST: if constexpr (H >= 128) rc = launch_dgrad_first<H>(d, n, stash, gx, s); break;
+        case Dgrad::FIRST_GENERAL:
+            if (H >= 128) tn::warn_once(4, "mlp backward: d loss / d x of a width-%d stack with %d inputs (encoding %d) on the general-shape kernel", H, a.in_dim, a.enc);
+            dgrad_layer_kernel<H, true, WPB><<<dim3((unsigned)blocks), dim3(WPB * 64), 0, s>>>(d, n, stash, gx);
+            rc = tn::check_launch("dgrad_layer_kernel(first)");
+            break;
         }
+        if (rc) return rc;
     }
     return TN_OK;
 }
@@ -1394,14 +1453,11 @@ int run_layers(const MlpArgs &a, const float *x, const float *aux, const float *
 extern "C" __attribute__((visibility("hidden"))) int64_t tn_mlp_bwd_layers_workspace_bytes(const tn_mlp_desc *desc, int64_t n)
 {
     if (!desc || n <= 0) return 0;
-    const int L = desc->n_layers, H = desc->dims[1];
-    if (L < 2 || L > TN_MLP_MAX_LAYERS) return 0;
-    if (H != 32 && H != 64 && H != 128 && H != 256) return 0;
-    for (int l = 1; l < L; ++l) if (desc->dims[l] != H) return 0;
-    if (((desc->dims[L] + 31) / 32) * (H / 32) > 64) return 0;          // weight-gradient tiling of the output layer (run_layers)
-    const int64_t rows = ws_rows(H, L, desc->encoding, desc->in_dim, (desc->dims[0] + 7) & ~7, desc->dims[L], (n + 31) / 32);
-    if (H == 128 || H == 256) return fused_pack_offset(rows) + tn::layers::fused_pack_bytes(H, L);       // (+ the packed weights of the cross-layer forward)
-    return rows * 32 * (int64_t)sizeof(float) + WS_TAIL_BYTES;
+    MlpArgs a;
+    int H = 0;
+    if (plan(desc, a, H) != TN_OK) return 0;
+    if (((a.out_dim + 31) / 32) * (H / 32) > 64) return 0;          // weight-gradient tiling of the output layer (make_plan)
+    return workspace(H, a, (n + 31) / 32).bytes;
 }
 
 extern "C" __attribute__((visibility("hidden"))) int tn_mlp_bwd_layers(const tn_mlp_desc *desc, const float *x, const float *aux,
@@ -1417,13 +1473,15 @@ extern "C" __attribute__((visibility("hidden"))) int tn_mlp_bwd_layers(const tn_
     TN_REQUIRE(a.enc != TN_ENC_DIR_CAT || aux, TN_E_NULL, "tn_mlp_bwd(layers): dir_cat needs aux");
     for (int l = 0; l < a.n_layers; ++l)
         TN_REQUIRE(grad_weights[l] && grad_biases[l], TN_E_NULL, "tn_mlp_bwd(layers): null gradient pointer");
+    Plan p;
+    if (int rc = make_plan(a, H, n, Pass::BWD, p, (desc->flags & TN_MLP_STASHED) != 0, (desc->flags & TN_MLP_GRAD_Y_ROWS) != 0, grad_x != nullptr))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
-    const bool stashed = (desc->flags & TN_MLP_STASHED) != 0, gy_rows = (desc->flags & TN_MLP_GRAD_Y_ROWS) != 0;
     switch (H) {
-    case 32: return run_layers<32>(a, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, workspace, s, stashed, gy_rows);
-    case 64: return run_layers<64>(a, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, workspace, s, stashed, gy_rows);
-    case 128: return run_layers<128>(a, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, workspace, s, stashed, gy_rows);
-    default: return run_layers<256>(a, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, workspace, s, stashed, gy_rows);
+    case 32: return run_bwd<32>(p, a, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, workspace, s);
+    case 64: return run_bwd<64>(p, a, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, workspace, s);
+    case 128: return run_bwd<128>(p, a, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, workspace, s);
+    default: return run_bwd<256>(p, a, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, workspace, s);
     }
 }
 
@@ -1431,15 +1489,13 @@ extern "C" int tn_mlp_rows_view(const tn_mlp_desc *desc, int64_t n, int64_t *y_r
 {
     TN_REQUIRE(desc && y_rows && grad_y_rows && tile_stride, TN_E_NULL, "tn_mlp_rows_view: null pointer");
     TN_REQUIRE(n >= 0, TN_E_SIZE, "tn_mlp_rows_view: negative n");
-    const int L = desc->n_layers;
-    TN_REQUIRE(L >= 2 && L <= TN_MLP_MAX_LAYERS, TN_E_CONFIG, "tn_mlp_rows_view: n_layers must be in [2, 12]");
-    const int H = desc->dims[1], out = desc->dims[L];
-    // the configurations whose training forward runs layer by layer and leaves y^T behind (run_fwd_only), see tn_mlp_fwd_stash
-    TN_REQUIRE(!two_pass_supported(desc) && tn_mlp_bwd_layers_workspace_bytes(desc, 32) > 0 && layer_kernel_path(H, L, out) &&
-                   (out & 31) == 0 && desc->out_activation == TN_ACT_NONE && desc->encoding != TN_ENC_AUX_CAT, TN_E_CONFIG,
+    MlpArgs a;
+    int H = 0;
+    if (int rc = plan(desc, a, H)) return rc;
+    // the configurations whose training forward runs layer by layer and leaves y^T behind (run_fwd), see tn_mlp_fwd_stash
+    TN_REQUIRE(layer_kernel_path(H, a) && (a.out_dim & 31) == 0 && a.out_act == TN_ACT_NONE && a.enc != TN_ENC_AUX_CAT, TN_E_CONFIG,
                "tn_mlp_rows_view: only wide stacks evaluated layer by layer (width 128 / 256, >= 3 layers, out % 32 == 0, no output activation) keep row views");
-    const int K0p = (desc->dims[0] + 7) & ~7;
-    const RowMap rm = make_rowmap(H, L, desc->encoding, desc->in_dim, K0p, out, (n + 31) / 32, slab_eligible(H, L, desc->encoding, desc->in_dim, K0p, out));
+    const RowMap rm = workspace(H, a, (n + 31) / 32).rm;
     *y_rows = rm.offGA() * 32;                 // buffer A: the last layer's (pre-)activation = y
     *grad_y_rows = rm.offGB() * 32;            // buffer B
     *tile_stride = (int64_t)rm.rows_total * 32;
@@ -1451,13 +1507,13 @@ extern "C" int tn_mlp_rows_view_hidden(const tn_mlp_desc *desc, int64_t n, int64
 {
     TN_REQUIRE(desc && h_rows && grad_h_rows && mask_rows && tile_stride, TN_E_NULL, "tn_mlp_rows_view_hidden: null pointer");
     TN_REQUIRE(n >= 0, TN_E_SIZE, "tn_mlp_rows_view_hidden: negative n");
-    const int L = desc->n_layers;
-    TN_REQUIRE(L >= 3 && L <= TN_MLP_MAX_LAYERS, TN_E_CONFIG, "tn_mlp_rows_view_hidden: n_layers must be in [3, 12]");
-    const int H = desc->dims[1], out = desc->dims[L], K0p = (desc->dims[0] + 7) & ~7;
-    TN_REQUIRE((desc->flags & TN_MLP_SKIP_LAST) && (desc->flags & TN_MLP_F16X2) && out == H && desc->out_activation == TN_ACT_NONE &&
-                   !two_pass_supported(desc) && slab_eligible(H, L, desc->encoding, desc->in_dim, K0p, out), TN_E_CONFIG,
+    MlpArgs a;
+    int H = 0;
+    if (int rc = plan(desc, a, H)) return rc;
+    TN_REQUIRE(a.skip_last && skip_last_ok(H, a) && a.out_act == TN_ACT_NONE, TN_E_CONFIG,
                "tn_mlp_rows_view_hidden: TN_MLP_SKIP_LAST | TN_MLP_F16X2 on a slab-layout stack (width 128 / 256, output as wide, no output activation)");
-    const RowMap rm = make_rowmap(H, L, desc->encoding, desc->in_dim, K0p, out, (n + 31) / 32, true);
+    const int L = a.n_layers;
+    const RowMap rm = workspace(H, a, (n + 31) / 32).rm;
     *h_rows = rm.offH(L - 2) * 32;
     *grad_h_rows = rm.offGB() * 32;
     *mask_rows = rm.offM(L - 2) * 32;
@@ -1470,16 +1526,12 @@ extern "C" int tn_mlp_rows_view_hidden(const tn_mlp_desc *desc, int64_t n, int64
 extern "C" int64_t tn_mlp_fwd_workspace_bytes(const tn_mlp_desc *desc, int64_t n)
 {
     if (!desc || n <= 0) return 0;
-    const int L = desc->n_layers;
-    if (L < 2 || L > TN_MLP_MAX_LAYERS) return 0;
-    const int H = desc->dims[1], out = desc->dims[L];
-    const int K0p = (desc->dims[0] + 7) & ~7;         // positional-encoding inputs, or plain inputs staged as rows (Cobafa's 36 features)
-    if ((H != 128 && H != 256) || !layer_kernel_path(H, L, out) || K0p > 64 ||
-        !(desc->encoding == TN_ENC_POSENC || plain_x_rows(H, L, desc->encoding, K0p, out))) return 0;
-    for (int l = 1; l < L; ++l) if (desc->dims[l] != H) return 0;
-    const Layout lay = make_layout(H, L, desc->encoding, desc->in_dim, (desc->dims[0] + 7) & ~7, out);
+    MlpArgs a;
+    int H = 0;
+    if (plan(desc, a, H) != TN_OK || !input_rows(H, a)) return 0;      // positional-encoding inputs, or plain inputs staged as rows (Cobafa's 36 features)
+    const Layout lay = make_layout(H, a.n_layers, a.enc, a.in_dim, a.K0_pad, a.out_dim);
     // the layer-wise form's ping-pong rows, then the packed weight stream of the cross-layer form (mlp_fused_f2.hip; 2.4 MB for Vanilla)
-    return infer_ws_rows_bytes(H, lay, (n + 31) / 32) + fused_pack_bytes(H, L);
+    return infer_ws_rows_bytes(H, lay, (n + 31) / 32) + fused_pack_bytes(H, a.n_layers);
 }
 
 extern "C" int tn_mlp_fwd_ws(const tn_mlp_desc *desc, const float *x, const float *aux, int64_t n, float *y, void *workspace,
@@ -1494,9 +1546,11 @@ extern "C" int tn_mlp_fwd_ws(const tn_mlp_desc *desc, const float *x, const floa
     MlpArgs a;
     int H = 0;
     if (int rc = plan(desc, a, H)) return rc;
+    Plan p;
+    if (int rc = make_plan(a, H, n, Pass::INFER_FWD, p)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if (H == 128) return run_fwd_only<128>(a, x, aux, n, y, (float *)workspace, s, true);
-    return run_fwd_only<256>(a, x, aux, n, y, (float *)workspace, s, true);
+    if (H == 128) return run_fwd<128>(p, a, x, aux, n, y, (float *)workspace, s);
+    return run_fwd<256>(p, a, x, aux, n, y, (float *)workspace, s);
 }
 
 // training forward of a stack the layer-by-layer form covers: y + activations + last pre-activation into the workspace
@@ -1509,11 +1563,13 @@ extern "C" __attribute__((visibility("hidden"))) int tn_mlp_fwd_stash_layers(con
     TN_REQUIRE(x && y && workspace, TN_E_NULL, "tn_mlp_fwd_stash(layers): null pointer");
     TN_REQUIRE(a.enc != TN_ENC_DIR_CAT || aux, TN_E_NULL, "tn_mlp_fwd_stash(layers): dir_cat needs aux");
     TN_REQUIRE(a.enc != TN_ENC_AUX_CAT, TN_E_CONFIG, "tn_mlp_fwd_stash(layers): aux_cat is only implemented for the two-pass form");
+    Plan p;
+    if (int rc = make_plan(a, H, n, Pass::TRAIN_FWD, p)) return rc;
     hipStream_t s = (hipStream_t)stream;
     switch (H) {
-    case 32: return run_fwd_only<32>(a, x, aux, n, y, workspace, s);
-    case 64: return run_fwd_only<64>(a, x, aux, n, y, workspace, s);
-    case 128: return run_fwd_only<128>(a, x, aux, n, y, workspace, s);
-    default: return run_fwd_only<256>(a, x, aux, n, y, workspace, s);
+    case 32: return run_fwd<32>(p, a, x, aux, n, y, workspace, s);
+    case 64: return run_fwd<64>(p, a, x, aux, n, y, workspace, s);
+    case 128: return run_fwd<128>(p, a, x, aux, n, y, workspace, s);
+    default: return run_fwd<256>(p, a, x, aux, n, y, workspace, s);
     }
 }

@@ -822,8 +822,9 @@ template <int H>
 int launch_chain(const FusedArgs &f, int64_t n, hipStream_t s)
 {
     constexpr int NW = NWAVES<H, true>;
+    // (f.L <= TN_MLP_MAX_LAYERS: ring + maxima table <= 4 x 32 KiB + 12 x 256 x 8 B + 64 B always fit)
+    static_assert(NRING * CHUNK_B + TN_MLP_MAX_LAYERS * 256 * NW + 64 <= LDS_LIMIT_BYTES, "fused chain: LDS");
     const size_t lds_bytes = (size_t)NRING * CHUNK_B + (size_t)f.L * 256 * NW + 64;
-    if (lds_bytes > (size_t)LDS_LIMIT_BYTES) return tn::fail(TN_E_CONFIG, "mlp_bwd(fused chain): maxima table does not fit LDS");
     auto kern = fused_chain_kernel<H>;
     hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) { tn::set_error("mlp_bwd(fused chain): cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
@@ -837,8 +838,9 @@ template <int H, bool STASH>
 int launch(const FusedArgs &f, int64_t n, hipStream_t s)
 {
     constexpr int NW = NWAVES<H, !STASH>;
+    // (f.L <= TN_MLP_MAX_LAYERS: ring + bias table + maxima table always fit)
+    static_assert(NRING * CHUNK_B + TN_MLP_MAX_LAYERS * H * 4 + (STASH ? TN_MLP_MAX_LAYERS * 256 * NW : 0) + 64 <= LDS_LIMIT_BYTES, "fused forward: LDS");
     const size_t lds_bytes = (size_t)NRING * CHUNK_B + (size_t)f.L * H * 4 + (STASH ? (size_t)f.L * 256 * NW : 0) + 64;
-    if (lds_bytes > (size_t)LDS_LIMIT_BYTES) return tn::fail(TN_E_CONFIG, "mlp_fwd(fused): bias table does not fit LDS");
     auto kern = fused_fwd_kernel<H, STASH>;
     hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) { tn::set_error("mlp_fwd(fused): cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
@@ -859,14 +861,6 @@ __attribute__((visibility("hidden"))) int64_t fused_pack_bytes(int H, int L)
     const int64_t pairs = (int64_t)(H / 32) * KS0 + (int64_t)(L - 1) * (H / 32) * (H / 16);
     const int64_t chunks = (pairs + CHUNK_PAIRS - 1) / CHUNK_PAIRS;
     return chunks * CHUNK_B + (int64_t)L * H * 4 + (int64_t)L * 16 + 256;
-}
-
-__attribute__((visibility("hidden"))) bool fused_fwd_ok(int H, const MlpArgs &a)
-{
-    if (!(H == 128 || H == 256) || !a.f2 || a.n_layers < 3 || a.n_layers > TN_MLP_MAX_LAYERS || a.out_dim != H || a.out_act != TN_ACT_NONE) return false;
-    if (a.K[0] > 64 || a.N[0] != H) return false;
-    for (int l = 1; l < a.n_layers; ++l) if (a.K[l] != H || a.N[l] != H) return false;
-    return true;
 }
 
 // Inference (spec == nullptr): e_rows = 64 rows x 32 samples per tile, contiguous over the tiles; y [n][H].  Training forward: spec says

@@ -119,7 +119,6 @@ struct FusedChain {                 // data-gradient chain: chain position i = l
 };
 int launch_fused_chain_f2(int H, const tn::mlp::MlpArgs &a, int top, int64_t n, void *pack_area, hipStream_t s, const FusedChain *spec);
 int64_t fused_pack_bytes(int H, int L);
-bool fused_fwd_ok(int H, const tn::mlp::MlpArgs &a);
 int launch_fused_fwd_f2(int H, const tn::mlp::MlpArgs &a, int64_t n, const float *e_rows, float *y, void *pack_area, hipStream_t s, const FusedStash *spec = nullptr);
 
 }  // namespace layers

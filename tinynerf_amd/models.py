@@ -108,6 +108,8 @@ class _FusedMLP(Function):
         # `recording` = torch.is_grad_enabled() at the call site: inside torch.no_grad() (infer(), the occupancy refresh)
         # needs_input_grad still reports the parameters' flags, and inside Function.forward grad mode is always off
         if _FusedMLP.stash_forward and recording and any(ctx.needs_input_grad) and n > 0:
+            if _FusedMLP.layerwise_training:        # (before the sizing: the workspace of a TN_MLP_LAYERWISE stack has no cross-layer area)
+                desc.flags |= L.MLP_LAYERWISE
             wsfn = L.lib().tn_mlp_bwd_workspace_bytes
             wsfn.restype = C.c_int64
             ws_bytes = int(wsfn(C.byref(desc), C.c_int64(_bucket(n))))
@@ -116,8 +118,6 @@ class _FusedMLP(Function):
             # forward's backward before the next forward of the module, so one buffer per module is enough
             ws = scratch[0].get(scratch[1], (ws_bytes // 4,), dev) if scratch is not None else torch.empty(ws_bytes // 4, device=dev)
             link = scratch[2] if scratch is not None and len(scratch) > 2 else None
-            if _FusedMLP.layerwise_training:
-                desc.flags |= L.MLP_LAYERWISE
             if rows_only and link is not None:
                 desc.flags |= L.MLP_ROWS_ONLY
                 if skip_last:
