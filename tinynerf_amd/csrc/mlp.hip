@@ -618,108 +618,92 @@ __global__ void posenc_kernel(const float *__restrict__ x, int64_t n, int C, con
     out[e] = is_cos ? cosf(ang) : sinf(ang);
 }
 
-template <int H>
-int launch_fwd(const MlpArgs &a_in, const float *x, const float *aux, int64_t n, float *y, float *pre_act, float *stash, hipStream_t s,
-               const FwdPair *pair = nullptr, const KpFwd *kp = nullptr)
-{
-    const int64_t n_tiles = (n + 31) / 32;
-    MlpArgs a = a_in;
+using FwdKern = decltype(&mlp_fwd_kernel<32, false, 16, false>);
+
+// A forward call as planned: the prepared heads and the one kernel that runs them
+struct FwdPlan {
+    MlpArgs a;
     FwdPair pr;
-    pr.aux = nullptr; pr.y = nullptr; pr.stash = nullptr;
-    if (pair) pr = *pair;
-    // f16x2 heads (TN_MLP_F16X2, mlp_f2_heads.h): same launch, the weights staged as fp16 hi / lo planes
+    KpFwd kp;
+    FwdKern kern;
+    int waves;
+    size_t lds;
+    int64_t blocks;
+    const char *what;
+};
+
+// first layer on plain input columns: no encoding evaluated in the kernel
+bool plain_cols(const MlpArgs &m) { return m.enc == TN_ENC_AUX_CAT || (m.enc == TN_ENC_NONE && (m.in_dim & 3) == 0); }
+
+// f16x2 heads (TN_MLP_F16X2, mlp_f2_heads.h): every head qualifies and both still fit LDS with their weights as fp16 hi / lo planes
+// (they always do for the reference's heads; otherwise the fp32 form runs)
+bool f2_heads(const MlpArgs &a, const MlpArgs *b, bool kp) {
+    if (!(f2_head_ok(a, 64) && (!b || f2_head_ok(*b, 64)) && (!kp || a.in_dim == 96))) return false;
+    MlpArgs fa = a, fb = b ? *b : a;
+    plan_f2(fa, 64); plan_f2(fb, 64);
+    return ((size_t)fa.lds_floats + (b ? (size_t)fb.lds_floats : 0)) * 4 <= (size_t)LDS_LIMIT_BYTES;
+}
+
+template <int H>
+int plan_fwd(FwdPlan &p, int64_t n, bool stash, bool pair, bool kp)
+{
+    MlpArgs &a = p.a;
     bool f2 = false;
-    if constexpr (H == 64) {
-        f2 = f2_head_ok(a, H) && (!pair || f2_head_ok(pr.b, H)) && (!kp || a.in_dim == 96);
-        if (f2) { plan_f2(a, H); if (pair) plan_f2(pr.b, H); }
-    }
-    size_t lds_bytes = (size_t)a.lds_floats * 4;
-    if (pair) lds_bytes += (size_t)pr.b.lds_floats * 4; else pr.b = a;
-    if (f2 && lds_bytes > (size_t)LDS_LIMIT_BYTES) {       // (cannot happen for the reference's heads; keep the fp32 form otherwise)
-        f2 = false; a = a_in; if (pair) pr = *pair; else pr.b = a;
-        lds_bytes = (size_t)a.lds_floats * 4 + (pair ? (size_t)pr.b.lds_floats * 4 : 0);
-    }
-    const bool wlds = lds_bytes <= (size_t)LDS_LIMIT_BYTES && a.enc != -1;
-    auto plain_cols = [](const MlpArgs &m) { return m.enc == TN_ENC_AUX_CAT || (m.enc == TN_ENC_NONE && (m.in_dim & 3) == 0); };
-    const bool fast = wlds && plain_cols(a) && (!pair || plain_cols(pr.b));
+    if constexpr (H == 64) f2 = f2_heads(a, pair ? &p.pr.b : nullptr, kp);
+    if (f2) { plan_f2(a, H); if (pair) plan_f2(p.pr.b, H); }
+    if (!pair) p.pr.b = a;
+    p.lds = ((size_t)a.lds_floats + (pair ? (size_t)p.pr.b.lds_floats : 0)) * 4;
+    const bool wlds = p.lds <= (size_t)LDS_LIMIT_BYTES && a.enc != -1;
+    const bool fast = wlds && plain_cols(a) && (!pair || plain_cols(p.pr.b));
     constexpr int WPB = H <= 64 ? 16 : 4;     // 16 waves share one LDS copy of the weights: 4 waves per SIMD
+    p.waves = WPB; p.what = "mlp_fwd_kernel";
     if (a.x_from_rows && !(wlds && stash && H == 64 && !kp))
         return tn::fail(TN_E_CONFIG, "mlp forward: TN_MLP_X_FROM_ROWS is only read by tn_mlp_fwd_stash of a width-64 f16x2 head");
-    if (wlds && stash) {
-        if constexpr (H == 64) {
-            // stash variants: 12 waves (170-VGPR budget) for the generic first layer, 16 for the plain-column one (119 VGPRs)
-            auto launch = [&](auto kern, int wps) -> int {
-                hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                if (e != hipSuccess) { tn::set_error("mlp: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(LDS_LIMIT_BYTES / lds_bytes, 2048 / (wps * 64)));
-                const int64_t blocks = std::min<int64_t>((n_tiles + wps - 1) / wps, 256 * per_cu);
-                kern<<<dim3((unsigned)blocks), dim3(wps * 64), lds_bytes, s>>>(a, x, aux, n, y, pre_act, stash, pr, KpFwd());
-                return TN_OK;
-            };
-            int rc;
-            if (kp) {                   // gather fused in: 12 waves (170-VGPR budget: 48 registers hold the tile's features)
-                if (!(fast && pair)) return tn::fail(TN_E_CONFIG, "tn_kplanes_mlp_fwd_pair: both heads must take the plain-column first layer");
-                auto go = [&](auto kern, int wv) -> int {
-                    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                    if (e != hipSuccess) { tn::set_error("mlp: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-                    const int64_t blocks = std::min<int64_t>((n_tiles + wv - 1) / wv, 256);
-                    kern<<<dim3((unsigned)blocks), dim3(wv * 64), lds_bytes, s>>>(a, x, aux, n, y, pre_act, stash, pr, *kp);
-                    return TN_OK;
-                };
-                // fp32 heads: 12 waves (8 waves x 256 VGPRs measured the same: 0.86 ms)
-                if (a.lean && !f2) return tn::fail(TN_E_CONFIG, "TN_MLP_LEAN needs the f16x2 heads (TN_MLP_F16X2)");
-                const int rc = f2 ? (a.lean ? go(mlp_fwd_kernel<H, true, TN_F2_KP_WAVES, true, true, true, true, true, 0, true>, TN_F2_KP_WAVES)
-                                            : go(mlp_fwd_kernel<H, true, TN_F2_KP_WAVES, true, true, true, true, true>, TN_F2_KP_WAVES))
-                                  : go(mlp_fwd_kernel<H, true, 12, true, true, true, true>, 12);
-                if (rc) return rc;
-                return tn::check_launch("mlp_fwd_kernel(kplanes)");
-            }
+    if (!wlds) {                              // weights streamed from L2
+        if (stash) return tn::fail(TN_E_CONFIG, "tn_mlp_fwd_stash: weights must fit LDS");
+        p.kern = mlp_fwd_kernel<H, false, WPB, false>; p.lds = 0; p.blocks = grid_blocks(n, WPB, 256 * 2);
+        return TN_OK;
+    }
+    if constexpr (H == 64) {
+        if (stash && kp) {                    // gather fused in: 12 waves (170-VGPR budget: 48 registers hold the tile's features)
+            if (!(fast && pair)) return tn::fail(TN_E_CONFIG, "tn_kplanes_mlp_fwd_pair: both heads must take the plain-column first layer");
+            // fp32 heads: 12 waves (8 waves x 256 VGPRs measured the same: 0.86 ms)
+            if (a.lean && !f2) return tn::fail(TN_E_CONFIG, "TN_MLP_LEAN needs the f16x2 heads (TN_MLP_F16X2)");
+            p.kern = f2 ? (a.lean ? mlp_fwd_kernel<H, true, TN_F2_KP_WAVES, true, true, true, true, true, 0, true>
+                                  : mlp_fwd_kernel<H, true, TN_F2_KP_WAVES, true, true, true, true, true>)
+                        : mlp_fwd_kernel<H, true, 12, true, true, true, true>;
+            p.waves = f2 ? TN_F2_KP_WAVES : 12; p.blocks = grid_blocks(n, p.waves, 256); p.what = "mlp_fwd_kernel(kplanes)";
+            return TN_OK;
+        }
+        if (stash) {        // 12 waves (170-VGPR budget) for the generic first layer, 16 for the plain-column one (119 VGPRs)
             if (a.x_from_rows && !(f2 && !pair && a.x_rows != nullptr && (a.in_dim == 256 || a.in_dim == 128)))
                 return tn::fail(TN_E_CONFIG, "tn_mlp_fwd_stash: TN_MLP_X_FROM_ROWS needs an f16x2 head with 128 or 256 inputs and x_rows");
             if (a.lean && !(f2 && pair)) return tn::fail(TN_E_CONFIG, "TN_MLP_LEAN needs the paired f16x2 heads (TN_MLP_F16X2, tn_mlp_fwd_stash_pair)");
-            if (a.lean) rc = launch(mlp_fwd_kernel<H, true, 12, true, true, true, false, true, 0, true>, 12);
-            else if (f2 && !pair && a.in_dim == 256) rc = launch(mlp_fwd_kernel<H, true, 8, true, false, true, false, true, 16>, 8);      // (x: 128 VGPRs)
-            else if (f2 && !pair && a.in_dim == 128) rc = launch(mlp_fwd_kernel<H, true, 12, true, false, true, false, true, 8>, 12);
-            else if (f2) rc = pair ? launch(mlp_fwd_kernel<H, true, 12, true, true, true, false, true>, 12) : launch(mlp_fwd_kernel<H, true, 12, true, false, true, false, true>, 12);
-            else if (fast) rc = pair ? launch(mlp_fwd_kernel<H, true, 16, true, true, true>, 16) : launch(mlp_fwd_kernel<H, true, 16, true, false, true>, 16);
-            else rc = pair ? launch(mlp_fwd_kernel<H, true, 12, true, true, false>, 12) : launch(mlp_fwd_kernel<H, true, 12, true, false, false>, 12);
-            if (rc) return rc;
-        } else return tn::fail(TN_E_CONFIG, "tn_mlp_fwd_stash: the register-resident training forward is built for width 64");
-    } else if (wlds && kp) {      // inference: gather + one head (the sigma head; the colour head then reads the feature rows where w > 0)
-        if constexpr (H == 64) {          // ... or gather + BOTH heads, nothing stashed, no feature rows (pair != nullptr)
+            p.waves = 12;
+            if (a.lean) p.kern = mlp_fwd_kernel<H, true, 12, true, true, true, false, true, 0, true>;
+            else if (f2 && !pair && a.in_dim == 256) { p.kern = mlp_fwd_kernel<H, true, 8, true, false, true, false, true, 16>; p.waves = 8; }  // (x: 128 VGPRs)
+            else if (f2 && !pair && a.in_dim == 128) p.kern = mlp_fwd_kernel<H, true, 12, true, false, true, false, true, 8>;
+            else if (f2) p.kern = pair ? mlp_fwd_kernel<H, true, 12, true, true, true, false, true> : mlp_fwd_kernel<H, true, 12, true, false, true, false, true>;
+            else if (fast) { p.kern = pair ? mlp_fwd_kernel<H, true, 16, true, true, true> : mlp_fwd_kernel<H, true, 16, true, false, true>; p.waves = 16; }
+            else p.kern = pair ? mlp_fwd_kernel<H, true, 12, true, true, false> : mlp_fwd_kernel<H, true, 12, true, false, false>;
+            p.blocks = grid_per_cu(n, p.waves, p.lds);
+            return TN_OK;
+        }
+        if (kp) {           // inference: gather + one head (the sigma head; the colour head then reads the feature rows where w > 0)
+            // ... or gather + BOTH heads, nothing stashed, no feature rows (pair)
             if (!fast) return tn::fail(TN_E_CONFIG, "tn_kplanes_mlp_fwd: the head must take the plain-column first layer");
-            auto go = [&](auto kern, int wv) -> int {
-                hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                if (e != hipSuccess) { tn::set_error("mlp: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-                const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(LDS_LIMIT_BYTES / lds_bytes, 2048 / (wv * 64)));
-                const int64_t blocks = std::min<int64_t>((n_tiles + wv - 1) / wv, 256 * per_cu);
-                kern<<<dim3((unsigned)blocks), dim3(wv * 64), lds_bytes, s>>>(a, x, aux, n, y, pre_act, stash, pr, *kp);
-                return TN_OK;
-            };
             // (the f16x2 pair holds the fp16 features beside both heads' tiles: 8 waves x 256 VGPRs, as in training)
-            const int rc = f2 ? (pair ? go(mlp_fwd_kernel<H, true, TN_F2_KP_WAVES, false, true, true, true, true>, TN_F2_KP_WAVES)
-                                      : go(mlp_fwd_kernel<H, true, 12, false, false, true, true, true>, 12))
-                              : (pair ? go(mlp_fwd_kernel<H, true, 12, false, true, true, true>, 12)
-                                      : go(mlp_fwd_kernel<H, true, 12, false, false, true, true>, 12));
-            if (rc) return rc;
-            return tn::check_launch("mlp_fwd_kernel(kplanes, inference)");
-        } else return tn::fail(TN_E_CONFIG, "tn_kplanes_mlp_fwd: width-64 heads only");
-    } else if (wlds) {
-        auto kern = fast ? mlp_fwd_kernel<H, true, WPB, false, false, true> : mlp_fwd_kernel<H, true, WPB, false, false, false>;
-        if constexpr (H == 64) { if (f2) kern = mlp_fwd_kernel<H, true, WPB, false, false, true, false, true>; }
-        hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) { tn::set_error("mlp: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-        const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(LDS_LIMIT_BYTES / lds_bytes, 2048 / (WPB * 64)));
-        const int64_t blocks = std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * per_cu);
-        kern<<<dim3((unsigned)blocks), dim3(WPB * 64), lds_bytes, s>>>(a, x, aux, n, y, pre_act, stash, pr, KpFwd());
-    } else {
-        if (stash) return tn::fail(TN_E_CONFIG, "tn_mlp_fwd_stash: weights must fit LDS");
-        // weights streamed from L2
-        auto kern = mlp_fwd_kernel<H, false, WPB, false>;
-        const int64_t blocks = std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * 2);
-        kern<<<dim3((unsigned)blocks), dim3(WPB * 64), 0, s>>>(a, x, aux, n, y, pre_act, nullptr, pr, KpFwd());
-    }
-    return tn::check_launch("mlp_fwd_kernel");
+            p.kern = f2 ? (pair ? mlp_fwd_kernel<H, true, TN_F2_KP_WAVES, false, true, true, true, true>
+                                : mlp_fwd_kernel<H, true, 12, false, false, true, true, true>)
+                        : (pair ? mlp_fwd_kernel<H, true, 12, false, true, true, true> : mlp_fwd_kernel<H, true, 12, false, false, true, true>);
+            p.waves = f2 && pair ? TN_F2_KP_WAVES : 12; p.blocks = grid_per_cu(n, p.waves, p.lds); p.what = "mlp_fwd_kernel(kplanes, inference)";
+            return TN_OK;
+        }
+    } else if (stash) return tn::fail(TN_E_CONFIG, "tn_mlp_fwd_stash: the register-resident training forward is built for width 64");
+    p.kern = fast ? mlp_fwd_kernel<H, true, WPB, false, false, true> : mlp_fwd_kernel<H, true, WPB, false, false, false>;
+    if constexpr (H == 64) { if (f2) p.kern = mlp_fwd_kernel<H, true, WPB, false, false, true, false, true>; }
+    p.blocks = grid_per_cu(n, WPB, p.lds);
+    return TN_OK;
 }
 
 // aux table of TN_ENC_AUX_CAT for the colour head: [PE(d), d, 0...] per ray
@@ -737,11 +721,12 @@ __global__ void dir_encode_kernel(const float *__restrict__ d, int64_t n, const 
 }
 
 int fwd_common(const tn_mlp_desc *desc, const float *x, const float *aux, int64_t n, float *y, float *pre_act, float *stash,
-               hipStream_t s, const char *who, const FwdPair *pair = nullptr, const KpFwd *kp = nullptr)
+               hipStream_t s, const FwdPair *pair = nullptr, const KpFwd *kp = nullptr)
 {
-    MlpArgs a;
+    FwdPlan p;
     int H = 0;
-    if (int rc = plan(desc, a, H)) return rc;
+    if (int rc = plan(desc, p.a, H)) return rc;
+    const MlpArgs &a = p.a;
     TN_REQUIRE(n >= 0, TN_E_SIZE, "tn_mlp_fwd: negative n");
     if (n == 0) return TN_OK;
     TN_REQUIRE((x || kp) && y, TN_E_NULL, "tn_mlp_fwd: null pointer");
@@ -749,12 +734,22 @@ int fwd_common(const tn_mlp_desc *desc, const float *x, const float *aux, int64_
     TN_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 15) == 0, TN_E_ALIGN, "tn_mlp_fwd: x / y must be 16-byte aligned");
     TN_REQUIRE(!kp || H == 64, TN_E_CONFIG, "tn_kplanes_mlp_fwd_pair: width-64 heads only");
     TN_REQUIRE(a.enc != TN_ENC_AUX_CAT || ((uintptr_t)aux & 15) == 0, TN_E_ALIGN, "tn_mlp_fwd: aux table must be 16-byte aligned");
-    switch (H) {
-    case 32: return launch_fwd<32>(a, x, aux, n, y, pre_act, stash, s, pair);
-    case 64: return launch_fwd<64>(a, x, aux, n, y, pre_act, stash, s, pair, kp);
-    case 128: return launch_fwd<128>(a, x, aux, n, y, pre_act, stash, s, pair);
-    default: return launch_fwd<256>(a, x, aux, n, y, pre_act, stash, s, pair);
-    }
+    p.pr.aux = nullptr; p.pr.y = nullptr; p.pr.stash = nullptr;
+    if (pair) p.pr = *pair;
+    if (kp) p.kp = *kp;
+    const int rc = H == 32 ? plan_fwd<32>(p, n, stash, pair, kp) : H == 64 ? plan_fwd<64>(p, n, stash, pair, kp)
+                 : H == 128 ? plan_fwd<128>(p, n, stash, pair, kp) : plan_fwd<256>(p, n, stash, pair, kp);
+    if (rc) return rc;
+    return launch(p.kern, p.waves, p.lds, p.blocks, s, p.what, p.a, x, aux, n, y, pre_act, stash, p.pr, p.kp);
+}
+
+// the second head of a pair: its prepared arguments and where its outputs go
+int partner_args(const tn_mlp_desc *partner, float *partner_y, void *partner_workspace, FwdPair &pr)
+{
+    int Hb = 0;
+    if (int rc = plan(partner, pr.b, Hb)) return rc;
+    pr.aux = nullptr; pr.y = partner_y; pr.stash = (float *)partner_workspace;
+    return TN_OK;
 }
 
 }  // namespace
@@ -762,7 +757,7 @@ int fwd_common(const tn_mlp_desc *desc, const float *x, const float *aux, int64_
 extern "C" int tn_mlp_fwd(const tn_mlp_desc *desc, const float *x, const float *aux, int64_t n, float *y, float *pre_act,
                           void *stream)
 {
-    return fwd_common(desc, x, aux, n, y, pre_act, nullptr, (hipStream_t)stream, "tn_mlp_fwd");
+    return fwd_common(desc, x, aux, n, y, pre_act, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int64_t tn_mlp_bwd_workspace_bytes(const tn_mlp_desc *desc, int64_t n);
@@ -774,22 +769,13 @@ extern "C" int tn_mlp_fwd_stash(const tn_mlp_desc *desc, const float *x, const f
                                 int64_t workspace_bytes, void *stream)
 {
     TN_REQUIRE(desc, TN_E_NULL, "tn_mlp_fwd_stash: null descriptor");
-    const int H = desc->dims[1];
     if (n <= 0) return n == 0 ? TN_OK : tn::fail(TN_E_SIZE, "tn_mlp_fwd_stash: negative n");
-    if (!two_pass_supported(desc)) {       // wide / deep stacks: the layer-by-layer backward's workspace
-        const int64_t need_l = tn_mlp_bwd_workspace_bytes(desc, n);
-        TN_REQUIRE(need_l > 0, TN_E_CONFIG, "tn_mlp_fwd_stash: this configuration's backward does not use a workspace");
-        TN_REQUIRE(workspace && workspace_bytes >= need_l, TN_E_NULL, "tn_mlp_fwd_stash: workspace missing or too small");
-        TN_REQUIRE(((uintptr_t)workspace & 15) == 0, TN_E_ALIGN, "tn_mlp_fwd_stash: workspace must be 16-byte aligned");
-        return tn_mlp_fwd_stash_layers(desc, x, aux, n, y, (float *)workspace, stream);
-    }
-    const int64_t need = tn_mlp_bwd_workspace_bytes(desc, n);
-    const int extra = extra_rows(desc->encoding, desc->in_dim, (desc->dims[0] + 7) & ~7);
-    TN_REQUIRE(need == ((n + 31) / 32) * (int64_t)stash_rows(H, desc->n_layers - 1, extra) * 128, TN_E_CONFIG,
-               "tn_mlp_fwd_stash: configuration not covered by the two-pass backward");
+    const int64_t need = tn_mlp_bwd_workspace_bytes(desc, n);       // (wide / deep stacks: the layer-by-layer backward's workspace)
+    TN_REQUIRE(need > 0, TN_E_CONFIG, "tn_mlp_fwd_stash: this configuration's backward does not use a workspace");
     TN_REQUIRE(workspace && workspace_bytes >= need, TN_E_NULL, "tn_mlp_fwd_stash: workspace missing or too small");
     TN_REQUIRE(((uintptr_t)workspace & 15) == 0, TN_E_ALIGN, "tn_mlp_fwd_stash: workspace must be 16-byte aligned");
-    return fwd_common(desc, x, aux, n, y, nullptr, (float *)workspace, (hipStream_t)stream, "tn_mlp_fwd_stash");
+    if (!two_pass_supported(desc)) return tn_mlp_fwd_stash_layers(desc, x, aux, n, y, (float *)workspace, stream);
+    return fwd_common(desc, x, aux, n, y, nullptr, (float *)workspace, (hipStream_t)stream);
 }
 
 extern "C" int tn_mlp_fwd_stash_pair(const tn_mlp_desc *desc, const tn_mlp_desc *partner, const float *x, const float *aux, int64_t n,
@@ -797,12 +783,8 @@ extern "C" int tn_mlp_fwd_stash_pair(const tn_mlp_desc *desc, const tn_mlp_desc 
                                      int64_t partner_workspace_bytes, void *stream)
 {
     TN_REQUIRE(desc && partner, TN_E_NULL, "tn_mlp_fwd_stash_pair: null descriptor");
-    const int H = desc->dims[1];
-    TN_REQUIRE(H == 64 && partner->dims[1] == 64 && desc->n_layers >= 2 && desc->n_layers <= 5 && partner->n_layers >= 2 &&
-                   partner->n_layers <= 5 && desc->dims[desc->n_layers] <= 4 && partner->dims[partner->n_layers] <= 4 &&
-                   partner->in_dim == desc->in_dim && (desc->in_dim & 3) == 0 &&
-                   (desc->encoding == TN_ENC_NONE || desc->encoding == TN_ENC_AUX_CAT) && partner->encoding == TN_ENC_NONE,
-               TN_E_CONFIG, "tn_mlp_fwd_stash_pair: two width-64 heads (<= 5 layers, <= 4 outputs) on the same x; partner without encoding");
+    TN_REQUIRE(fwd_pair_shape_ok(desc, partner), TN_E_CONFIG,
+               "tn_mlp_fwd_stash_pair: two width-64 heads (<= 5 layers, <= 4 outputs) on the same x; partner without encoding");
     if (n <= 0) return n == 0 ? TN_OK : tn::fail(TN_E_SIZE, "tn_mlp_fwd_stash_pair: negative n");
     const int64_t need_a = tn_mlp_bwd_workspace_bytes(desc, n), need_b = tn_mlp_bwd_workspace_bytes(partner, n);
     TN_REQUIRE(need_a > 0 && need_b > 0, TN_E_CONFIG, "tn_mlp_fwd_stash_pair: configuration not covered by the two-pass backward");
@@ -812,31 +794,8 @@ extern "C" int tn_mlp_fwd_stash_pair(const tn_mlp_desc *desc, const tn_mlp_desc 
                "tn_mlp_fwd_stash_pair: buffers must be 16-byte aligned");
     TN_REQUIRE(partner_y, TN_E_NULL, "tn_mlp_fwd_stash_pair: null pointer");
     FwdPair pr;
-    int Hb = 0;
-    if (int rc = plan(partner, pr.b, Hb)) return rc;
-    pr.aux = nullptr; pr.y = partner_y; pr.stash = (float *)partner_workspace;
-    return fwd_common(desc, x, aux, n, y, nullptr, (float *)workspace, (hipStream_t)stream, "tn_mlp_fwd_stash_pair", &pr);
-}
-
-static int kp_fwd_args(const tn_kplanes_desc *kd, const float *coords, int64_t coord_stride, float *feat, KpFwd &kp, const char *who)
-{
-    TN_REQUIRE(kd, TN_E_NULL, "tn_kplanes_mlp_fwd: null descriptor");
-    TN_REQUIRE(kd->n_scales == 3 && kd->channels == 32, TN_E_CONFIG, "tn_kplanes_mlp_fwd: 3 scales x 32 channels (run.py:136)");
-    TN_REQUIRE(coord_stride >= 3, TN_E_SIZE, "tn_kplanes_mlp_fwd: bad coordinate stride");
-    TN_REQUIRE(coords && feat, TN_E_NULL, "tn_kplanes_mlp_fwd: null pointer");
-    TN_REQUIRE(((uintptr_t)feat & 15) == 0, TN_E_ALIGN, "tn_kplanes_mlp_fwd: feat must be 16-byte aligned");
-    for (int s = 0; s < 3; ++s) {
-        TN_REQUIRE(kd->height[s] > 0 && kd->width[s] > 0 && (int64_t)kd->height[s] * kd->width[s] * 32 < (1ll << 30), TN_E_SIZE,
-                   "tn_kplanes_mlp_fwd: bad plane resolution");
-        kp.H[s] = kd->height[s]; kp.W[s] = kd->width[s];
-        for (int p = 0; p < 3; ++p) {
-            TN_REQUIRE(kd->planes[s][p], TN_E_NULL, "tn_kplanes_mlp_fwd: null plane pointer");
-            TN_REQUIRE(((uintptr_t)kd->planes[s][p] & 15) == 0, TN_E_ALIGN, "tn_kplanes_mlp_fwd: planes must be 16-byte aligned");
-            kp.planes[s][p] = kd->planes[s][p];
-        }
-    }
-    kp.coords = coords; kp.coord_stride = coord_stride; kp.feat = feat;
-    return TN_OK;
+    if (int rc = partner_args(partner, partner_y, partner_workspace, pr)) return rc;
+    return fwd_common(desc, x, aux, n, y, nullptr, (float *)workspace, (hipStream_t)stream, &pr);
 }
 
 extern "C" int tn_kplanes_mlp_fwd(const tn_kplanes_desc *kd, const float *coords, int64_t coord_stride, const tn_mlp_desc *desc, int64_t n,
@@ -846,10 +805,16 @@ extern "C" int tn_kplanes_mlp_fwd(const tn_kplanes_desc *kd, const float *coords
     TN_REQUIRE(desc->in_dim == 96 && desc->encoding == TN_ENC_NONE && desc->dims[1] == 64 && desc->row_gate == nullptr, TN_E_CONFIG,
                "tn_kplanes_mlp_fwd: an ungated width-64 head without encoding on the 96 features");
     if (n <= 0) return n == 0 ? TN_OK : tn::fail(TN_E_SIZE, "tn_kplanes_mlp_fwd: negative n");
+    TN_REQUIRE(kd, TN_E_NULL, "tn_kplanes_mlp_fwd: null descriptor");
+    TN_REQUIRE(kd->n_scales == 3 && kd->channels == 32, TN_E_CONFIG, "tn_kplanes_mlp_fwd: 3 scales x 32 channels (run.py:136)");
+    TN_REQUIRE(coord_stride >= 3, TN_E_SIZE, "tn_kplanes_mlp_fwd: bad coordinate stride");
+    TN_REQUIRE(coords && feat, TN_E_NULL, "tn_kplanes_mlp_fwd: null pointer");
+    TN_REQUIRE(((uintptr_t)feat & 15) == 0, TN_E_ALIGN, "tn_kplanes_mlp_fwd: feat must be 16-byte aligned");
     KpFwd kp;
-    if (int rc = kp_fwd_args(kd, coords, coord_stride, feat, kp, "tn_kplanes_mlp_fwd")) return rc;
+    if (int rc = kp_planes(kd, coords, coord_stride, kp)) return rc;
+    kp.feat = feat;
     TN_REQUIRE(y && ((uintptr_t)y & 15) == 0, TN_E_ALIGN, "tn_kplanes_mlp_fwd: y must be a 16-byte aligned pointer");
-    return fwd_common(desc, nullptr, nullptr, n, y, nullptr, nullptr, (hipStream_t)stream, "tn_kplanes_mlp_fwd", nullptr, &kp);
+    return fwd_common(desc, nullptr, nullptr, n, y, nullptr, nullptr, (hipStream_t)stream, nullptr, &kp);
 }
 
 extern "C" int tn_kplanes_mlp_fwd_pair(const tn_kplanes_desc *kd, const float *coords, int64_t coord_stride, const tn_mlp_desc *desc,
@@ -867,17 +832,8 @@ extern "C" int tn_kplanes_mlp_fwd_pair(const tn_kplanes_desc *kd, const float *c
     TN_REQUIRE(((uintptr_t)feat & 15) == 0, TN_E_ALIGN, "tn_kplanes_mlp_fwd_pair: feat must be 16-byte aligned");
     TN_REQUIRE(!inference || ((uintptr_t)coords & 15) == 0, TN_E_ALIGN, "tn_kplanes_mlp_fwd_pair: coords must be 16-byte aligned");
     KpFwd kp;
-    for (int s = 0; s < 3; ++s) {
-        TN_REQUIRE(kd->height[s] > 0 && kd->width[s] > 0 && (int64_t)kd->height[s] * kd->width[s] * 32 < (1ll << 30), TN_E_SIZE,
-                   "tn_kplanes_mlp_fwd_pair: bad plane resolution");
-        kp.H[s] = kd->height[s]; kp.W[s] = kd->width[s];
-        for (int p = 0; p < 3; ++p) {
-            TN_REQUIRE(kd->planes[s][p], TN_E_NULL, "tn_kplanes_mlp_fwd_pair: null plane pointer");
-            TN_REQUIRE(((uintptr_t)kd->planes[s][p] & 15) == 0, TN_E_ALIGN, "tn_kplanes_mlp_fwd_pair: planes must be 16-byte aligned");
-            kp.planes[s][p] = kd->planes[s][p];
-        }
-    }
-    kp.coords = coords; kp.coord_stride = coord_stride; kp.feat = feat;
+    if (int rc = kp_planes(kd, coords, coord_stride, kp)) return rc;
+    kp.feat = feat;
     if (inference) {        // no backward follows: no workspace rows, no feature rows (the dummy operand line points at the coordinates)
         kp.write_feat = 0;
         if (!feat) {
@@ -886,11 +842,8 @@ extern "C" int tn_kplanes_mlp_fwd_pair(const tn_kplanes_desc *kd, const float *c
         }
     }
     // the rest is tn_mlp_fwd_stash_pair with the x rows replaced by the gather
-    const int H = desc->dims[1];
-    TN_REQUIRE(H == 64 && partner->dims[1] == 64 && desc->n_layers >= 2 && desc->n_layers <= 5 && partner->n_layers >= 2 &&
-                   partner->n_layers <= 5 && desc->dims[desc->n_layers] <= 4 && partner->dims[partner->n_layers] <= 4 &&
-                   (desc->encoding == TN_ENC_NONE || desc->encoding == TN_ENC_AUX_CAT) && partner->encoding == TN_ENC_NONE,
-               TN_E_CONFIG, "tn_kplanes_mlp_fwd_pair: two width-64 heads (<= 5 layers, <= 4 outputs); partner without encoding");
+    TN_REQUIRE(fwd_pair_shape_ok(desc, partner), TN_E_CONFIG,
+               "tn_kplanes_mlp_fwd_pair: two width-64 heads (<= 5 layers, <= 4 outputs); partner without encoding");
     const int64_t need_a = tn_mlp_bwd_workspace_bytes(desc, n), need_b = tn_mlp_bwd_workspace_bytes(partner, n);
     TN_REQUIRE(need_a > 0 && need_b > 0, TN_E_CONFIG, "tn_kplanes_mlp_fwd_pair: configuration not covered by the two-pass backward");
     TN_REQUIRE(y && partner_y && (inference || (workspace && workspace_bytes >= need_a && partner_workspace && partner_workspace_bytes >= need_b)),
@@ -899,10 +852,8 @@ extern "C" int tn_kplanes_mlp_fwd_pair(const tn_kplanes_desc *kd, const float *c
     TN_REQUIRE((((uintptr_t)workspace | (uintptr_t)partner_workspace | (uintptr_t)partner_y | (uintptr_t)y) & 15) == 0, TN_E_ALIGN,
                "tn_kplanes_mlp_fwd_pair: buffers must be 16-byte aligned");
     FwdPair pr;
-    int Hb = 0;
-    if (int rc = plan(partner, pr.b, Hb)) return rc;
-    pr.aux = nullptr; pr.y = partner_y; pr.stash = (float *)partner_workspace;
-    return fwd_common(desc, nullptr, aux, n, y, nullptr, (float *)workspace, (hipStream_t)stream, "tn_kplanes_mlp_fwd_pair", &pr, &kp);
+    if (int rc = partner_args(partner, partner_y, partner_workspace, pr)) return rc;
+    return fwd_common(desc, nullptr, aux, n, y, nullptr, (float *)workspace, (hipStream_t)stream, &pr, &kp);
 }
 
 extern "C" int tn_dir_encode(const float *dirs, int64_t n, const float *freqs, int n_freqs, float *out, int stride, void *stream)

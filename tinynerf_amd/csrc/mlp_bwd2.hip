@@ -34,6 +34,9 @@ extern "C" int tn_heads_dx_rows(const float *w_a, int ld_a, int col0_a, const fl
 extern "C" int tn_mlp_wgrad_lean_pair(const tn_mlp_desc *desc, const tn_mlp_desc *partner, const float *x, const float *aux, int64_t n,
                                       float *const *gw, float *const *gb, float *const *gws, float *const *gbs, const float *ws_a,
                                       const float *ws_b, void *stream);
+extern "C" int tn_mlp_wgrad_lean_check(const tn_mlp_desc *desc, const tn_mlp_desc *partner, const float *x, const float *aux, int64_t n,
+                                       float *const *gw, float *const *gb, float *const *gws, float *const *gbs, const float *ws_a,
+                                       const float *ws_b);
 extern "C" int tn_mlp_wgrad_rows(const float *g_rows, int64_t g_stride, int ng, const float *a_rows, int64_t a_stride, int na, float *gW,
                                  int ldw, int col0, int kmax, float *gB, int64_t n, void *stream);
 
@@ -928,9 +931,6 @@ WgradPlan wgrad_plan(int enc, int in_dim, int K0_pad, int H, int NH, bool x_else
     return p;
 }
 
-bool v2_supported(const tn_mlp_desc *d) { return two_pass_supported(d); }
-
-// phase bit 0: data-gradient chain, bit 1: weight gradient.  pair != nullptr: the chain also runs head `pair->b`.
 // first layer of a head without its aux columns: the stashed chain only ever reads W_0's x columns (W_0^T G_0 over the x
 // slots), and the 14 KB this saves in LDS are what the fused scatter's per-wave tiles need
 MlpArgs compact_first_layer(const MlpArgs &a)
@@ -967,24 +967,29 @@ int launch_chain_g0b(const MlpArgs &b, const MlpArgs &a, const float *x, const f
     PairArgs pr;
     pr.b = first_layer_only(a); pr.gy = nullptr; pr.stash = const_cast<float *>(g0_rows_a); pr.g0_stride = g0_stride_a;
     const size_t lds_bytes = ((size_t)b.lds_floats + (size_t)pr.b.lds_floats) * 4;
-    if (lds_bytes > (size_t)LDS_LIMIT_BYTES) return tn::fail(TN_E_CONFIG, "mlp_bwd: both first layers do not fit LDS");
-    auto kern = mlp_chain_kernel<64, 1, WPS, true, false, false, false, true>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(LDS_LIMIT_BYTES / lds_bytes, 2048 / (WPS * 64)));
-    const int64_t blocks = std::min<int64_t>((n_tiles + WPS - 1) / WPS, 256 * per_cu);
-    kern<<<dim3((unsigned)blocks), dim3(WPS * 64), lds_bytes, s>>>(b, x, nullptr, gy_b, n, gx, stash_b, pr, KpBwd());
-    return tn::check_launch("mlp_chain_kernel(g0b)");
+    return launch(mlp_chain_kernel<64, 1, WPS, true, false, false, false, true>, WPS, lds_bytes, grid_per_cu(n, WPS, lds_bytes), s,
+                  "mlp_chain_kernel(g0b)", b, x, nullptr, gy_b, n, gx, stash_b, pr, KpBwd());
 }
 
+// Workspace geometry of a width-64 head (two-pass form): floats per 32-sample tile, and where its G_0 rows start
+int64_t tile_floats(const MlpArgs &m) { return (int64_t)stash_rows(64, m.n_layers - 1, extra_rows(m.enc, m.in_dim, m.K0_pad)) * 32; }
+int64_t g0_floats(const MlpArgs &m) { return (int64_t)(m.n_layers - 1) * 64 * 32; }
+
+// The first layer's x-column weight gradient comes from x as rows of the producer's workspace (mlp_wgrad_rows.hip) ...
+bool x_cols_from_rows(const MlpArgs &a, bool stashed) {
+    return stashed && a.x_rows != nullptr && (a.in_dim == 128 || a.in_dim == 256) && x_slots(a.enc, a.in_dim) == a.in_dim;
+}
+// ... and for both heads of a pair in one launch (tn_mlp_wgrad_rows2)
+bool x_cols_from_rows2(const MlpArgs &a, const MlpArgs &b) {
+    return x_cols_from_rows(a, true) && b.x_rows == a.x_rows && b.x_rows_stride == a.x_rows_stride && extra_rows(a.enc, a.in_dim, a.K0_pad) == 0;
+}
+
+// data-gradient chain of head `a` (pair: with head `pair->b`; kpb: with the plane scatter inside)
 template <int H, int NH>
-int launch_v2(const MlpArgs &a, const tn_mlp_desc *d, const float *x, const float *aux, const float *gy, int64_t n,
-              float *const *gw, float *const *gb, float *gx, float *stash, bool stashed, hipStream_t s,
-              const PairArgs *pair = nullptr, int phase = 3, const KpBwd *kpb = nullptr)
+int launch_chain(const MlpArgs &a, const float *x, const float *aux, const float *gy, int64_t n, float *gx, float *stash, bool stashed,
+                 hipStream_t s, const PairArgs *pair = nullptr, const KpBwd *kpb = nullptr)
 {
-    const int64_t n_tiles = (n + 31) / 32;
-    if ((phase & 1) && kpb) {                 // paired, stashed chain with the plane scatter inside
+    if (kpb) {                                // paired, stashed chain with the plane scatter inside
         if constexpr (H == 64 && NH == 4) {
             if (!(pair && stashed && a.enc == TN_ENC_AUX_CAT && a.in_dim == 96)) return tn::fail(TN_E_CONFIG, "mlp_bwd: fused scatter needs the paired K-Planes heads");
             constexpr int WPK = 8;
@@ -993,14 +998,10 @@ int launch_v2(const MlpArgs &a, const tn_mlp_desc *d, const float *x, const floa
             pr.b = compact_first_layer(pair->b);
             const size_t lds_bytes = ((size_t)ac.lds_floats + (size_t)pr.b.lds_floats + (size_t)WPK * tn::KP_WAVE_LDS) * 4;
             if (lds_bytes > (size_t)LDS_LIMIT_BYTES) return tn::fail(TN_E_CONFIG, "mlp_bwd: weights + scatter tiles do not fit LDS");
-            auto kern = mlp_chain_kernel<H, NH, WPK, true, false, true, true>;
-            hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-            if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-            const int64_t blocks = std::min<int64_t>((n_tiles + WPK - 1) / WPK, 256);
-            kern<<<dim3((unsigned)blocks), dim3(WPK * 64), lds_bytes, s>>>(ac, x, aux, gy, n, gx, stash, pr, *kpb);
-            if (int rc = tn::check_launch("mlp_chain_kernel(kplanes)")) return rc;
+            return launch(mlp_chain_kernel<H, NH, WPK, true, false, true, true>, WPK, lds_bytes, grid_blocks(n, WPK, 256), s,
+                          "mlp_chain_kernel(kplanes)", ac, x, aux, gy, n, gx, stash, pr, *kpb);
         } else return tn::fail(TN_E_CONFIG, "mlp_bwd: fused scatter is built for the 5-layer colour head");
-    } else if (phase & 1) {
+    }
     size_t lds_bytes = (size_t)a.lds_floats * 4;
     constexpr int WPB = 8;
     constexpr int WPS = NH == 1 ? 10 : 16;   // stashed chain: no forward -> ~100 live registers: 4 waves per SIMD, or 2 x 10
@@ -1019,97 +1020,100 @@ int launch_v2(const MlpArgs &a, const tn_mlp_desc *d, const float *x, const floa
         lds_bytes += (size_t)pr.b.lds_floats * 4;
     } else pr.b = a;
     if (lds_bytes > (size_t)LDS_LIMIT_BYTES) return tn::fail(TN_E_CONFIG, "mlp_bwd: weights do not fit LDS");
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(LDS_LIMIT_BYTES / lds_bytes, 2048 / (wpb * 64)));
-    const int64_t blocks = std::min<int64_t>((n_tiles + wpb - 1) / wpb, 256 * per_cu);
-    kern<<<dim3((unsigned)blocks), dim3(wpb * 64), lds_bytes, s>>>(a, x, aux, gy, n, gx, stash, pr, KpBwd());
-    if (int rc = tn::check_launch("mlp_chain_kernel")) return rc;
-    }
-    if (!(phase & 2)) return TN_OK;
+    return launch(kern, wpb, lds_bytes, grid_per_cu(n, wpb, lds_bytes), s, "mlp_chain_kernel", a, x, aux, gy, n, gx, stash, pr, KpBwd());
+}
 
+// the reference's two decoder shapes (two_pass_supported): one hidden layer (sigma) or four (colour)
+int chain(const MlpArgs &a, const float *x, const float *aux, const float *gy, int64_t n, float *gx, float *stash, bool stashed,
+          hipStream_t s, const PairArgs *pair = nullptr, const KpBwd *kpb = nullptr)
+{
+    return a.n_layers == 2 ? launch_chain<64, 1>(a, x, aux, gy, n, gx, stash, stashed, s, pair, kpb)
+                           : launch_chain<64, 4>(a, x, aux, gy, n, gx, stash, stashed, s, pair, kpb);
+}
+
+using WgradKern = decltype(&mlp_wgrad_kernel<64, 1, 1, 8, 4, false>);
+
+// the weight-gradient launch of one head, planned before anything of the backward runs
+struct WgradStep {
     WgradArgs w;
+    bool rows;                 // x columns from rows (x_cols_from_rows): tn_mlp_wgrad_rows first, unless the pair took them
+    WgradKern kern;
+    int waves;
+    size_t lds;
+    int64_t blocks;
+    const char *what;
+};
+
+template <int H, int NH>
+int plan_wgrad(WgradStep &st, const MlpArgs &a, float *const *gw, float *const *gb, int64_t n, bool stashed)
+{
+    WgradArgs &w = st.w;
     constexpr int T = H / 32;
     w.n_layers = a.n_layers; w.in_dim = a.in_dim; w.K0 = a.K0; w.K0_pad = a.K0_pad; w.enc = a.enc; w.n_freqs = a.n_freqs;
     w.out_dim = a.out_dim;
     w.Tk0 = (a.K0_pad + 31) / 32;
-    w.tk_skip = 0;
     for (int l = 0; l < a.n_layers; ++l) { w.gW[l] = gw[l]; w.gB[l] = gb[l]; w.K[l] = a.K[l]; w.N[l] = a.N[l]; }
     w.aux_index = a.aux_index; w.aux_stride = a.aux_stride;
     // x as [feature][32-sample] rows (the workspace of the wide stack that produced it): the first layer's x columns -- all of
     // its k tiles below in_dim / 32 and its bias gradient -- go to the layer-kernel form (mlp_wgrad_rows.hip); what is left
     // here are the encoding columns, the hidden layers and the output layer
-    const bool x_rows = a.x_rows != nullptr && stashed && H == 64 && (a.in_dim & 31) == 0 && x_slots(a.enc, a.in_dim) == a.in_dim &&
-                        (a.in_dim == 128 || a.in_dim == 256);
-    if (x_rows) {
-        const int extra_r = extra_rows(a.enc, a.in_dim, a.K0_pad);
-        const int col0 = (a.enc == TN_ENC_DIR_CAT || a.enc == TN_ENC_AUX_CAT) ? a.K0 - a.in_dim : 0;      // torch order [PE(d), d, x]
-        if (a.x_wgrad_done) {}              // (tn_mlp_bwd_pair: both heads' x columns went out in one launch, tn_mlp_wgrad_rows2)
-        else if (int rc = tn_mlp_wgrad_rows(stash + (int64_t)NH * H * 32, (int64_t)stash_rows(H, NH, extra_r) * 32, H, a.x_rows, a.x_rows_stride,
-                                       a.in_dim, gw[0], a.K0, col0, a.in_dim, gb[0], n, s)) return rc;
-        w.tk_skip = a.in_dim / 32;
-    }
+    st.rows = x_cols_from_rows(a, stashed);
+    w.tk_skip = st.rows ? a.in_dim / 32 : 0;
     w.total_tiles = T * (w.Tk0 - w.tk_skip) + (NH - 1) * T * T + T;
-    const WgradPlan wp = wgrad_plan(a.enc, a.in_dim, a.K0_pad, H, NH, x_rows);
-    const size_t wlds = wp.lds;
-    if (wlds > (size_t)LDS_LIMIT_BYTES) return tn::fail(TN_E_CONFIG, "mlp_bwd: workspace tile does not fit LDS");
+    const WgradPlan wp = wgrad_plan(a.enc, a.in_dim, a.K0_pad, H, NH, st.rows);
+    if (wp.lds > (size_t)LDS_LIMIT_BYTES) return tn::fail(TN_E_CONFIG, "mlp_bwd: workspace tile does not fit LDS");
     if (wp.xs > 0 && (a.in_dim & 3)) return tn::fail(TN_E_CONFIG, "mlp_bwd: in_dim must be a multiple of 4");
-    const int chunks = wp.chunks;
-    const int64_t wblocks = std::min<int64_t>(n_tiles, 256 * (wlds * 2 <= (size_t)LDS_LIMIT_BYTES ? 2 : 1));
-    const int extra_rows_ = extra_rows(a.enc, a.in_dim, a.K0_pad);
-    if (extra_rows_ == 0 && (wp.xs > 0 || (x_rows && a.enc == TN_ENC_AUX_CAT)) && NH >= 2) {   // double-buffered, paired form (measured slower for the 2-layer sigma head)
+    const bool aux = a.enc == TN_ENC_AUX_CAT;
+    st.what = "mlp_wgrad_kernel";
+    if (extra_rows(a.enc, a.in_dim, a.K0_pad) == 0 && (wp.xs > 0 || (st.rows && aux)) && NH >= 2) {   // double-buffered, paired form (measured slower for the 2-layer sigma head)
         if constexpr (H == 64 && NH >= 2) {                // paired ownership: one wave per shared operand
             constexpr int RG4 = H + NH * H + 4;
-            const int xw4 = x_rows ? 0 : a.in_dim;         // (x tiles from row views: nothing of x is staged)
-            const size_t lds4 = 2 * ((size_t)RG4 * RS + 32 * (size_t)xw4 + 32 * (size_t)wp.aw) * 4 + 32 * 16;
-            const int chunks4 = RG4 * 8 + 8 * xw4;
-            if (lds4 <= (size_t)LDS_LIMIT_BYTES && w.Tk0 - w.tk_skip + (NH - 1) * 2 + 1 <= 12 && chunks4 <= 5 * 768) {
-                auto wk = a.enc == TN_ENC_AUX_CAT ? mlp_wgrad4_kernel<NH, 12, 5, true> : mlp_wgrad4_kernel<NH, 12, 5, false>;
-                hipError_t we = hipFuncSetAttribute((const void *)wk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
-                if (we != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds4, hipGetErrorString(we)); return (int)we; }
-                wk<<<dim3((unsigned)std::min<int64_t>(n_tiles, 256)), dim3(12 * 64), lds4, s>>>(w, x, aux, n, stash);
-                return tn::check_launch("mlp_wgrad4_kernel");
+            const int xw4 = st.rows ? 0 : a.in_dim;        // (x tiles from row views: nothing of x is staged)
+            st.lds = 2 * ((size_t)RG4 * RS + 32 * (size_t)xw4 + 32 * (size_t)wp.aw) * 4 + 32 * 16;
+            if (st.lds <= (size_t)LDS_LIMIT_BYTES && w.Tk0 - w.tk_skip + (NH - 1) * 2 + 1 <= 12 && RG4 * 8 + 8 * xw4 <= 5 * 768) {
+                st.kern = aux ? mlp_wgrad4_kernel<NH, 12, 5, true> : mlp_wgrad4_kernel<NH, 12, 5, false>;
+                st.waves = 12; st.blocks = grid_blocks(n, 1, 256); st.what = "mlp_wgrad4_kernel";
+                return TN_OK;
             }
         }
     }
-#define TN_WGRAD_X(MAXS_, NW_, NCH_, AUX_)                                                                                 \
-    do {                                                                                                                    \
-        auto wk = mlp_wgrad_kernel<H, NH, MAXS_, NW_, NCH_, AUX_>;                                                         \
-        hipError_t we = hipFuncSetAttribute((const void *)wk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds);      \
-        if (we != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", wlds, hipGetErrorString(we)); return (int)we; } \
-        wk<<<dim3((unsigned)wblocks), dim3(NW_ * 64), wlds, s>>>(w, x, aux, n, stash);                                      \
-    } while (0)
-#define TN_WGRAD(MAXS_, NW_, NCH_) TN_WGRAD_X(MAXS_, NW_, NCH_, false)
-    if (a.enc == TN_ENC_AUX_CAT) {
-        // per-ray table columns + hidden + output layers of a head whose x columns went to the row-operand kernel above (the
-        // colour head behind a 256- / 128-wide stack): the general tiling with the table rows staged per tile
+    // tilings of the general kernel: accumulator tiles per wave, waves, float4 chunks staged per wave (12 waves x 2 tiles: 170-VGPR
+    // budget, no spills)
+    struct Tiling { int max_tiles, max_chunks; WgradKern kern; int waves; };
+    const Tiling tilings[] = {
+        {8, 4 * 512, mlp_wgrad_kernel<H, NH, 1, 8, 4, false>, 8},    {16, 4 * 1024, mlp_wgrad_kernel<H, NH, 1, 16, 4, false>, 16},
+        {24, 7 * 768, mlp_wgrad_kernel<H, NH, 2, 12, 7, false>, 12}, {32, 6 * 1024, mlp_wgrad_kernel<H, NH, 2, 16, 6, false>, 16},
+        {48, 10 * 1024, mlp_wgrad_kernel<H, NH, 3, 16, 10, false>, 16}};
+    st.lds = wp.lds; st.blocks = grid_blocks(n, 1, 256 * (wp.lds * 2 <= (size_t)LDS_LIMIT_BYTES ? 2 : 1));
+    if (aux) {
+        // per-ray table columns + hidden + output layers of a head whose x columns went to the row-operand kernel (the colour head
+        // behind a 256- / 128-wide stack): the general tiling with the table rows staged per tile
         if constexpr (NH == 4) {
-            if (x_rows && w.total_tiles <= 24 && chunks <= 7 * 768 && wp.aw <= 64) {
-                TN_WGRAD_X(2, 12, 7, true);
-                return tn::check_launch("mlp_wgrad_kernel(aux)");
+            if (st.rows && w.total_tiles <= 24 && wp.chunks <= 7 * 768 && wp.aw <= 64) {
+                st.kern = mlp_wgrad_kernel<H, NH, 2, 12, 7, true>; st.waves = 12; st.what = "mlp_wgrad_kernel(aux)";
+                return TN_OK;
             }
         }
         return tn::fail(TN_E_CONFIG, "mlp_bwd: TN_ENC_AUX_CAT outside the paired weight-gradient tiling");
     }
-    if (w.total_tiles <= 8 && chunks <= 4 * 512) TN_WGRAD(1, 8, 4);
-    else if (w.total_tiles <= 16 && chunks <= 4 * 1024) TN_WGRAD(1, 16, 4);
-    else if (w.total_tiles <= 24 && chunks <= 7 * 768) TN_WGRAD(2, 12, 7);     // 12 waves x 2 tiles: 170-VGPR budget, no spills
-    else if (w.total_tiles <= 32 && chunks <= 6 * 1024) TN_WGRAD(2, 16, 6);
-    else if (w.total_tiles <= 48 && chunks <= 10 * 1024) TN_WGRAD(3, 16, 10);
-    else return tn::fail(TN_E_CONFIG, "mlp_bwd: configuration outside the wgrad tiling");
-#undef TN_WGRAD
-#undef TN_WGRAD_X
-    return tn::check_launch("mlp_wgrad_kernel");
+    for (const Tiling &t : tilings)
+        if (w.total_tiles <= t.max_tiles && wp.chunks <= t.max_chunks) { st.kern = t.kern; st.waves = t.waves; return TN_OK; }
+    return tn::fail(TN_E_CONFIG, "mlp_bwd: configuration outside the wgrad tiling");
 }
 
-template <int H>
-int launch_v2_h(const MlpArgs &a, const tn_mlp_desc *d, const float *x, const float *aux, const float *gy, int64_t n,
-                float *const *gw, float *const *gb, float *gx, float *stash, bool stashed, hipStream_t s,
-                const PairArgs *pair = nullptr, int phase = 3, const KpBwd *kpb = nullptr)
+int plan_wgrad(WgradStep &st, const MlpArgs &a, float *const *gw, float *const *gb, int64_t n, bool stashed)
 {
-    // the reference's two decoder shapes (two_pass_supported): one hidden layer (sigma) or four (colour)
-    if (a.n_layers == 2) return launch_v2<H, 1>(a, d, x, aux, gy, n, gw, gb, gx, stash, stashed, s, pair, phase, kpb);
-    return launch_v2<H, 4>(a, d, x, aux, gy, n, gw, gb, gx, stash, stashed, s, pair, phase, kpb);
+    return a.n_layers == 2 ? plan_wgrad<64, 1>(st, a, gw, gb, n, stashed) : plan_wgrad<64, 4>(st, a, gw, gb, n, stashed);
+}
+
+int run_wgrad(const WgradStep &st, const MlpArgs &a, const float *x, const float *aux, int64_t n, float *stash, hipStream_t s)
+{
+    if (st.rows && !a.x_wgrad_done) {        // (x_wgrad_done: tn_mlp_bwd_pair took both heads' x columns in one launch, tn_mlp_wgrad_rows2)
+        const int col0 = (a.enc == TN_ENC_DIR_CAT || a.enc == TN_ENC_AUX_CAT) ? a.K0 - a.in_dim : 0;      // torch order [PE(d), d, x]
+        if (int rc = tn_mlp_wgrad_rows(stash + g0_floats(a), tile_floats(a), 64, a.x_rows, a.x_rows_stride, a.in_dim, st.w.gW[0], a.K0, col0,
+                                       a.in_dim, st.w.gB[0], n, s)) return rc;
+    }
+    return launch(st.kern, st.waves, st.lds, st.blocks, s, st.what, st.w, x, aux, n, stash);
 }
 
 }  // namespace
@@ -1117,7 +1121,7 @@ int launch_v2_h(const MlpArgs &a, const tn_mlp_desc *d, const float *x, const fl
 extern "C" int64_t tn_mlp_bwd_workspace_bytes(const tn_mlp_desc *desc, int64_t n)
 {
     if (n <= 0 || !desc) return 0;
-    if (!v2_supported(desc)) {
+    if (!two_pass_supported(desc)) {
         if (desc->encoding == TN_ENC_AUX_CAT) return 0;
         return tn_mlp_bwd_layers_workspace_bytes(desc, n);
     }
@@ -1133,14 +1137,14 @@ extern "C" int tn_mlp_bwd(const tn_mlp_desc *desc, const float *x, const float *
     TN_REQUIRE(desc, TN_E_NULL, "tn_mlp_bwd: null descriptor");
     const int64_t need = tn_mlp_bwd_workspace_bytes(desc, n);
     const bool stashed = (desc->flags & TN_MLP_STASHED) != 0;
-    const bool v2 = v2_supported(desc);
+    const bool two_pass = two_pass_supported(desc);
     if (stashed || desc->encoding == TN_ENC_AUX_CAT) {
-        TN_REQUIRE(v2 || (stashed && desc->encoding != TN_ENC_AUX_CAT && need > 0), TN_E_CONFIG,
+        TN_REQUIRE(two_pass || (stashed && desc->encoding != TN_ENC_AUX_CAT && need > 0), TN_E_CONFIG,
                    "tn_mlp_bwd: TN_ENC_AUX_CAT needs a configuration of the two-pass form, TN_MLP_STASHED one with a workspace");
         if (n == 0) return TN_OK;
         TN_REQUIRE(workspace && workspace_bytes >= need, TN_E_NULL, "tn_mlp_bwd: TN_MLP_STASHED / TN_ENC_AUX_CAT need the workspace");
     }
-    if (!v2) {                                                 // wide / deep / odd-shaped stack (or its stash): layer-by-layer form
+    if (!two_pass) {                                           // wide / deep / odd-shaped stack (or its stash): layer-by-layer form
         if (n == 0) return TN_OK;
         TN_REQUIRE(need > 0, TN_E_CONFIG, "tn_mlp_bwd: unsupported layer configuration");
         TN_REQUIRE(workspace && workspace_bytes >= need, TN_E_NULL, "tn_mlp_bwd: this configuration needs the workspace");
@@ -1159,7 +1163,11 @@ extern "C" int tn_mlp_bwd(const tn_mlp_desc *desc, const float *x, const float *
     for (int l = 0; l < a.n_layers; ++l)
         TN_REQUIRE(grad_weights[l] && grad_biases[l], TN_E_NULL, "tn_mlp_bwd: null gradient pointer");
     hipStream_t s = (hipStream_t)stream;
-    return launch_v2_h<64>(a, desc, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, (float *)workspace, stashed, s);
+    float *ws = (float *)workspace;
+    WgradStep w;
+    if (int rc = plan_wgrad(w, a, grad_weights, grad_biases, n, stashed)) return rc;
+    if (int rc = chain(a, x, aux, grad_y, n, grad_x, ws, stashed, s)) return rc;
+    return run_wgrad(w, a, x, aux, n, ws, s);
 }
 
 static int bwd_pair_common(const tn_mlp_desc *desc, const tn_mlp_desc *partner, const float *x, const float *aux,
@@ -1171,7 +1179,7 @@ static int bwd_pair_common(const tn_mlp_desc *desc, const tn_mlp_desc *partner, 
     TN_REQUIRE(desc && partner, TN_E_NULL, "tn_mlp_bwd_pair: null descriptor");
     TN_REQUIRE((desc->flags & TN_MLP_STASHED) && (partner->flags & TN_MLP_STASHED), TN_E_CONFIG,
                "tn_mlp_bwd_pair: both heads need TN_MLP_STASHED workspaces (tn_mlp_fwd_stash)");
-    TN_REQUIRE(v2_supported(desc) && v2_supported(partner), TN_E_CONFIG, "tn_mlp_bwd_pair: outside the two-pass form's configurations");
+    TN_REQUIRE(two_pass_supported(desc) && two_pass_supported(partner), TN_E_CONFIG, "tn_mlp_bwd_pair: outside the two-pass form's configurations");
     TN_REQUIRE(desc->n_layers == 5 && partner->n_layers == 2 && partner->encoding == TN_ENC_NONE && partner->in_dim == desc->in_dim &&
                    partner->dims[1] == desc->dims[1] && desc->dims[1] == 64 && (desc->in_dim & 31) == 0 && desc->encoding != TN_ENC_POSENC,
                TN_E_CONFIG, "tn_mlp_bwd_pair: a 5-layer head and a 2-layer partner on the same x (width 64, in_dim % 32 == 0)");
@@ -1190,21 +1198,35 @@ static int bwd_pair_common(const tn_mlp_desc *desc, const tn_mlp_desc *partner, 
     for (int l = 0; l < b.n_layers; ++l)
         TN_REQUIRE(partner_grad_weights[l] && partner_grad_biases[l], TN_E_NULL, "tn_mlp_bwd_pair: null gradient pointer");
     hipStream_t s = (hipStream_t)stream;
+    float *ws_a = (float *)workspace, *ws_b = (float *)partner_workspace;
     PairArgs pr;
-    pr.b = b; pr.gy = partner_grad_y; pr.stash = (float *)partner_workspace;
+    pr.b = b; pr.gy = partner_grad_y; pr.stash = ws_b;
     a.accum_gx = 0;
-    const bool chain = !(desc->flags & TN_MLP_WGRAD_ONLY), wgrad = !(desc->flags & TN_MLP_CHAIN_ONLY);
-    TN_REQUIRE(chain || wgrad, TN_E_CONFIG, "tn_mlp_bwd_pair: TN_MLP_CHAIN_ONLY and TN_MLP_WGRAD_ONLY exclude each other");
+    const bool chain_half = !(desc->flags & TN_MLP_WGRAD_ONLY), wgrad = !(desc->flags & TN_MLP_CHAIN_ONLY);
+    TN_REQUIRE(chain_half || wgrad, TN_E_CONFIG, "tn_mlp_bwd_pair: TN_MLP_CHAIN_ONLY and TN_MLP_WGRAD_ONLY exclude each other");
     const bool lean = (desc->flags & TN_MLP_LEAN) != 0;
     TN_REQUIRE(lean == ((partner->flags & TN_MLP_LEAN) != 0), TN_E_CONFIG, "tn_mlp_bwd_pair: TN_MLP_LEAN must be set on both heads or on neither");
     if (lean) {
         // the workspaces hold no H rows (the forward ran with TN_MLP_LEAN): the chain half needs none; the weight-gradient half
         // rebuilds them from the feature rows (mlp_wgrad_rc.hip)
-        if (chain)
-            if (int rc = launch_v2_h<64>(a, desc, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, (float *)workspace, true, s, &pr, 1, kpb)) return rc;
+        if (wgrad)
+            if (int rc = tn_mlp_wgrad_lean_check(desc, partner, x, aux, n, grad_weights, grad_biases, partner_grad_weights,
+                                                 partner_grad_biases, ws_a, ws_b)) return rc;
+        if (chain_half)
+            if (int rc = chain(a, x, aux, grad_y, n, grad_x, ws_a, true, s, &pr, kpb)) return rc;
         if (!wgrad) return TN_OK;
         return tn_mlp_wgrad_lean_pair(desc, partner, x, aux, n, grad_weights, grad_biases, partner_grad_weights, partner_grad_biases,
-                                      (const float *)workspace, (const float *)partner_workspace, stream);
+                                      ws_a, ws_b, stream);
+    }
+    // weight gradients, planned before anything runs.  First layers over the x columns: with x as rows of the producer's workspace
+    // both heads' tiles go out in ONE launch (x is 80 % of what a single-head launch reads at 256 columns)
+    MlpArgs aw = a, bw = b;
+    const bool rows2 = x_cols_from_rows2(a, b);
+    if (rows2) { aw.x_wgrad_done = 1; bw.x_wgrad_done = 1; }
+    WgradStep wa, wb;
+    if (wgrad) {
+        if (int rc = plan_wgrad(wa, aw, grad_weights, grad_biases, n, true)) return rc;
+        if (int rc = plan_wgrad(wb, bw, partner_grad_weights, partner_grad_biases, n, true)) return rc;
     }
     // Heads behind a wide stack (x and grad_x as rows of its workspace): the colour head's chain runs WITHOUT its grad_x part (no first
     // layer in LDS), and the sigma head's launch adds W_0c^T G_0c -- G_0c read back as rows -- to its own W_0s^T G_0s and writes the sum
@@ -1214,51 +1236,40 @@ static int bwd_pair_common(const tn_mlp_desc *desc, const tn_mlp_desc *partner, 
                             a.enc == TN_ENC_AUX_CAT && (a.in_dim & 31) == 0 &&
                             ((size_t)b.lds_floats + (size_t)first_layer_only(a).lds_floats) * 4 <= (size_t)LDS_LIMIT_BYTES;
     const bool fits = kpb != nullptr || ((size_t)a.lds_floats + (size_t)b.lds_floats) * 4 <= (size_t)LDS_LIMIT_BYTES;
-    if (chain) {
+    if (chain_half) {
         if (rows_split) {
             MlpArgs a0 = a;
             a0.gx_rows = nullptr;                 // (no grad_x output: the launch stops at G_0)
-            if (int rc = launch_v2_h<64>(a0, desc, x, aux, grad_y, n, grad_weights, grad_biases, nullptr, (float *)workspace, true, s, nullptr, 1)) return rc;
+            if (int rc = chain(a0, x, aux, grad_y, n, nullptr, ws_a, true, s)) return rc;
             if (a.f2 && b.f2 && (a.in_dim == 128 || a.in_dim == 256)) {
                 // f16x2: the sigma head's chain stops at G_0 as well, and grad_x = W_0c[:, x]^T G_0c + W_0s^T G_0s is a launch of its own on
                 // the fp16 matrix cores (heads_dx.hip): 6 k instead of 33 k matrix-pipe cycles per tile, bound by the rows it writes
                 MlpArgs b0 = b;
                 b0.gx_rows = nullptr;
-                if (int rc = launch_v2_h<64>(b0, partner, x, nullptr, partner_grad_y, n, partner_grad_weights, partner_grad_biases, nullptr,
-                                             (float *)partner_workspace, true, s, nullptr, 1)) return rc;
+                if (int rc = chain(b0, x, nullptr, partner_grad_y, n, nullptr, ws_b, true, s)) return rc;
                 const int col0 = a.K0 - a.in_dim;                    // torch order [PE(d), d, x]
-                if (int rc = tn_heads_dx_rows(desc->weights[0], a.K0, col0, partner->weights[0], b.K0, 0,
-                                              (const float *)workspace + (int64_t)4 * 64 * 32, (int64_t)stash_rows(64, 4, 0) * 32,
-                                              (const float *)partner_workspace + (int64_t)1 * 64 * 32, (int64_t)stash_rows(64, 1, 0) * 32, a.in_dim,
-                                              a.gx_rows, a.gx_rows_stride, a.gx_mask_rows, a.gx_mask_stride, n, s)) return rc;
-            } else if (int rc = launch_chain_g0b(b, a, x, partner_grad_y, n, nullptr, (float *)partner_workspace,
-                                                 (const float *)workspace + (int64_t)4 * 64 * 32, (int64_t)stash_rows(64, 4, 0) * 32, s)) return rc;
+                if (int rc = tn_heads_dx_rows(desc->weights[0], a.K0, col0, partner->weights[0], b.K0, 0, ws_a + g0_floats(a), tile_floats(a),
+                                              ws_b + g0_floats(b), tile_floats(b), a.in_dim, a.gx_rows, a.gx_rows_stride, a.gx_mask_rows,
+                                              a.gx_mask_stride, n, s)) return rc;
+            } else if (int rc = launch_chain_g0b(b, a, x, partner_grad_y, n, nullptr, ws_b, ws_a + g0_floats(a), tile_floats(a), s)) return rc;
         } else if (fits) {
-            if (int rc = launch_v2_h<64>(a, desc, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, (float *)workspace, true, s, &pr, 1, kpb)) return rc;
+            if (int rc = chain(a, x, aux, grad_y, n, grad_x, ws_a, true, s, &pr, kpb)) return rc;
         } else {
-            if (int rc = launch_v2_h<64>(a, desc, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, (float *)workspace, true, s, nullptr, 1)) return rc;
+            if (int rc = chain(a, x, aux, grad_y, n, grad_x, ws_a, true, s)) return rc;
             MlpArgs b1 = b;
             b1.accum_gx = 1;
-            if (int rc = launch_v2_h<64>(b1, partner, x, nullptr, partner_grad_y, n, partner_grad_weights, partner_grad_biases, grad_x,
-                                         (float *)partner_workspace, true, s, nullptr, 1)) return rc;
+            if (int rc = chain(b1, x, nullptr, partner_grad_y, n, grad_x, ws_b, true, s)) return rc;
         }
     }
     if (!wgrad) return TN_OK;
-    // first layers over the x columns: with x as rows of the producer's workspace both heads' tiles go out in ONE launch (x is 80 % of
-    // what a single-head launch reads at 256 columns)
-    MlpArgs aw = a, bw = b;
-    if (a.x_rows != nullptr && b.x_rows == a.x_rows && a.x_rows_stride == b.x_rows_stride && (a.in_dim == 128 || a.in_dim == 256) &&
-        x_slots(a.enc, a.in_dim) == a.in_dim && extra_rows(a.enc, a.in_dim, a.K0_pad) == 0) {
+    if (rows2) {
         const int col0 = (a.enc == TN_ENC_DIR_CAT || a.enc == TN_ENC_AUX_CAT) ? a.K0 - a.in_dim : 0;      // torch order [PE(d), d, x]
-        if (int rc = tn_mlp_wgrad_rows2((const float *)workspace + (int64_t)4 * 64 * 32, (int64_t)stash_rows(64, 4, 0) * 32,
-                                        (const float *)partner_workspace + (int64_t)1 * 64 * 32, (int64_t)stash_rows(64, 1, 0) * 32,
-                                        a.x_rows, a.x_rows_stride, a.in_dim, grad_weights[0], a.K0, col0, grad_biases[0],
-                                        partner_grad_weights[0], b.K0, 0, partner_grad_biases[0], n, s)) return rc;
-        aw.x_wgrad_done = 1; bw.x_wgrad_done = 1;
+        if (int rc = tn_mlp_wgrad_rows2(ws_a + g0_floats(a), tile_floats(a), ws_b + g0_floats(b), tile_floats(b), a.x_rows, a.x_rows_stride,
+                                        a.in_dim, grad_weights[0], a.K0, col0, grad_biases[0], partner_grad_weights[0], b.K0, 0,
+                                        partner_grad_biases[0], n, s)) return rc;
     }
-    if (int rc = launch_v2_h<64>(aw, desc, x, aux, grad_y, n, grad_weights, grad_biases, grad_x, (float *)workspace, true, s, &pr, 2, kpb)) return rc;
-    return launch_v2_h<64>(bw, partner, x, nullptr, partner_grad_y, n, partner_grad_weights, partner_grad_biases, nullptr,
-                           (float *)partner_workspace, true, s, nullptr, 2);
+    if (int rc = run_wgrad(wa, aw, x, aux, n, ws_a, s)) return rc;
+    return run_wgrad(wb, bw, x, nullptr, n, ws_b, s);
 }
 
 extern "C" int tn_mlp_bwd_pair(const tn_mlp_desc *desc, const tn_mlp_desc *partner, const float *x, const float *aux,
@@ -1286,18 +1297,9 @@ extern "C" int tn_kplanes_mlp_bwd_pair(const tn_kplanes_desc *kd, const float *c
     if (n == 0) return TN_OK;
     TN_REQUIRE(coords, TN_E_NULL, "tn_kplanes_mlp_bwd_pair: null coordinates");
     KpBwd kp;
-    for (int s = 0; s < 3; ++s) {
-        TN_REQUIRE(kd->height[s] > 0 && kd->width[s] > 0 && (int64_t)kd->height[s] * kd->width[s] * 32 < (1ll << 30), TN_E_SIZE,
-                   "tn_kplanes_mlp_bwd_pair: bad plane resolution");
-        kp.H[s] = kd->height[s]; kp.W[s] = kd->width[s];
-        for (int p = 0; p < 3; ++p) {
-            TN_REQUIRE(kd->planes[s][p], TN_E_NULL, "tn_kplanes_mlp_bwd_pair: null plane pointer");
-            TN_REQUIRE(((uintptr_t)kd->planes[s][p] & 15) == 0, TN_E_ALIGN, "tn_kplanes_mlp_bwd_pair: planes must be 16-byte aligned");
-            kp.planes[s][p] = kd->planes[s][p];
-            kp.grads[s][p] = grad_planes[s][p];           // NULL: no gradient for that plane
-        }
-    }
-    kp.coords = coords; kp.coord_stride = coord_stride;
+    if (int rc = kp_planes(kd, coords, coord_stride, kp)) return rc;
+    for (int s = 0; s < 3; ++s)
+        for (int p = 0; p < 3; ++p) kp.grads[s][p] = grad_planes[s][p];       // NULL: no gradient for that plane
     return bwd_pair_common(desc, partner, feat, aux, grad_y, partner_grad_y, n, grad_weights, grad_biases, partner_grad_weights,
                            partner_grad_biases, grad_feat, workspace, workspace_bytes, partner_workspace, partner_workspace_bytes, stream,
                            &kp);

@@ -197,6 +197,51 @@ inline bool two_pass_supported(const tn_mlp_desc *d) {
     return true;
 }
 
+// Forward pair (tn_mlp_fwd_stash_pair, tn_kplanes_mlp_fwd_pair): two width-64 heads of 2 .. 5 layers and <= 4 outputs on the same x;
+// `d` without encoding or with a per-ray table, `p` without encoding
+inline bool fwd_pair_shape_ok(const tn_mlp_desc *d, const tn_mlp_desc *p) {
+    auto head = [](const tn_mlp_desc *m) { return m->dims[1] == 64 && m->n_layers >= 2 && m->n_layers <= 5 && m->dims[m->n_layers] <= 4; };
+    return head(d) && head(p) && p->in_dim == d->in_dim && (d->in_dim & 3) == 0 && (d->encoding == TN_ENC_NONE || d->encoding == TN_ENC_AUX_CAT) &&
+           p->encoding == TN_ENC_NONE;
+}
+
+// the K-Planes gather fused into the heads (KpFwd / KpBwd): 3 scales x 32 channels, every plane present and 16-byte aligned
+template <class Kp>
+int kp_planes(const tn_kplanes_desc *kd, const float *coords, int64_t coord_stride, Kp &kp)
+{
+    for (int s = 0; s < 3; ++s) {
+        TN_REQUIRE(kd->height[s] > 0 && kd->width[s] > 0 && (int64_t)kd->height[s] * kd->width[s] * 32 < (1ll << 30), TN_E_SIZE,
+                   "K-Planes heads: bad plane resolution");
+        kp.H[s] = kd->height[s]; kp.W[s] = kd->width[s];
+        for (int p = 0; p < 3; ++p) {
+            TN_REQUIRE(kd->planes[s][p], TN_E_NULL, "K-Planes heads: null plane pointer");
+            TN_REQUIRE(((uintptr_t)kd->planes[s][p] & 15) == 0, TN_E_ALIGN, "K-Planes heads: planes must be 16-byte aligned");
+            kp.planes[s][p] = kd->planes[s][p];
+        }
+    }
+    kp.coords = coords; kp.coord_stride = coord_stride;
+    return TN_OK;
+}
+
+// blocks of a launch over n samples in 32-sample tiles, `waves` tiles per block and round, at most `cap` blocks ...
+inline int64_t grid_blocks(int64_t n, int waves, int64_t cap) { return std::min<int64_t>(((n + 31) / 32 + waves - 1) / waves, cap); }
+// ... or as many blocks per CU (256 CUs) as the LDS and 2048 threads per CU allow
+inline int64_t grid_per_cu(int64_t n, int waves, size_t lds) {
+    return grid_blocks(n, waves, 256 * (int64_t)std::max<size_t>(1, std::min<size_t>(LDS_LIMIT_BYTES / lds, 2048 / (waves * 64))));
+}
+
+// the one way a planned kernel is launched: reserve its dynamic LDS (if any), launch, check
+template <class... P, class... A>
+int launch(void (*kern)(P...), int waves, size_t lds, int64_t blocks, hipStream_t s, const char *what, A... args)
+{
+    if (lds) {
+        const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) { tn::set_error("%s: cannot reserve %zu B of LDS: %s", what, lds, hipGetErrorString(e)); return (int)e; }
+    }
+    kern<<<dim3((unsigned)blocks), dim3(waves * 64), lds, s>>>(args...);
+    return tn::check_launch(what);
+}
+
 inline int plan(const tn_mlp_desc *d, MlpArgs &a, int &H)
 {
     TN_REQUIRE(d, TN_E_NULL, "mlp: null descriptor");

@@ -655,72 +655,80 @@ __global__ __launch_bounds__(512) void wgrad_first_kernel(FlArgs p)
 
 }  // namespace
 
+// The lean rule: the reference's decoders (run.py:133-139) as f16x2 heads (TN_MLP_F16X2): colour 147 -> 64 x 4 -> 3 on [per-ray table
+// (51), x (96)], sigma 96 -> 64 -> 1
+static bool lean_pair_ok(const tn_mlp_desc *d, const tn_mlp_desc *p)
+{
+    const bool f2 = (d->flags & TN_MLP_F16X2) && (p->flags & TN_MLP_F16X2);
+    return f2 && d->n_layers == 5 && p->n_layers == 2 && d->in_dim == 96 && p->in_dim == 96 && d->encoding == TN_ENC_AUX_CAT &&
+           p->encoding == TN_ENC_NONE && d->dims[0] == 147 && d->dims[1] == 64 && d->dims[2] == 64 && d->dims[3] == 64 &&
+           d->dims[4] == 64 && d->dims[5] == 3 && p->dims[0] == 96 && p->dims[1] == 64 && p->dims[2] == 1 &&
+           d->aux_stride >= FL_AW && (d->aux_stride & 3) == 0;
+}
+
 // 1 when tn_mlp_bwd_pair / tn_kplanes_mlp_bwd_pair can run `desc` / `partner` under TN_MLP_LEAN (callers decide the forward's form with it)
 extern "C" int tn_mlp_lean_supported(const tn_mlp_desc *desc, const tn_mlp_desc *partner)
 {
-    if (!desc || !partner) return 0;
-    const bool f2 = (desc->flags & TN_MLP_F16X2) && (partner->flags & TN_MLP_F16X2);
-    return f2 && desc->n_layers == 5 && partner->n_layers == 2 && desc->in_dim == 96 && partner->in_dim == 96 && desc->encoding == TN_ENC_AUX_CAT &&
-           partner->encoding == TN_ENC_NONE && desc->dims[0] == 147 && desc->dims[1] == 64 && desc->dims[2] == 64 && desc->dims[3] == 64 &&
-           desc->dims[4] == 64 && desc->dims[5] == 3 && partner->dims[0] == 96 && partner->dims[1] == 64 && partner->dims[2] == 1 &&
-           desc->aux_stride >= 56 && (desc->aux_stride & 3) == 0;
+    return desc && partner && lean_pair_ok(desc, partner);
 }
 
-// Weight / bias gradients of the paired heads under TN_MLP_LEAN: `desc` = the 5-layer head (TN_ENC_AUX_CAT or TN_ENC_NONE on 96 inputs),
-// `partner` = the 2-layer head on the same x; workspaces as the chain half of tn_mlp_bwd_pair left them.  Gradients accumulate (+=).
+// every refusal of tn_mlp_wgrad_lean_pair, before anything runs; `p` as the launches take it
+static int lean_plan(RcArgs &p, const tn_mlp_desc *desc, const tn_mlp_desc *partner, const float *x, const float *aux, int64_t n,
+                     float *const *gw, float *const *gb, float *const *gws, float *const *gbs, const float *ws_a, const float *ws_b)
+{
+    TN_REQUIRE(desc && partner && x && gw && gb && gws && gbs && ws_a && ws_b, TN_E_NULL, "tn_mlp_wgrad_lean_pair: null pointer");
+    int Ha = 0, Hb = 0;
+    if (int rc = plan(desc, p.a, Ha)) return rc;
+    if (int rc = plan(partner, p.b, Hb)) return rc;
+    TN_REQUIRE(lean_pair_ok(desc, partner), TN_E_CONFIG, "TN_MLP_LEAN: the reference's decoders (run.py:133-139) as f16x2 heads (TN_MLP_F16X2): "
+                                                         "colour 147 -> 64 x 4 -> 3 on [per-ray table (51), x (96)], sigma 96 -> 64 -> 1");
+    TN_REQUIRE(aux && ((uintptr_t)aux & 15) == 0 && p.a.aux_index, TN_E_NULL, "TN_MLP_LEAN: aux table (16-byte aligned) and aux_index are required");
+    TN_REQUIRE((((uintptr_t)x | (uintptr_t)ws_a | (uintptr_t)ws_b) & 15) == 0, TN_E_ALIGN, "TN_MLP_LEAN: x / workspaces must be 16-byte aligned");
+    if (n <= 0) return TN_OK;
+    for (int l = 0; l < 5; ++l) TN_REQUIRE(gw[l] && gb[l], TN_E_NULL, "TN_MLP_LEAN: null gradient pointer");
+    TN_REQUIRE(gws[0] && gbs[0] && gws[1] && gbs[1], TN_E_NULL, "TN_MLP_LEAN: null gradient pointer");
+    plan_f2(p.a, 64);
+    plan_f2(p.b, 64);
+    TN_REQUIRE(((size_t)p.a.lds_floats + (size_t)p.b.lds_floats) * 4 <= (size_t)LDS_LIMIT_BYTES, TN_E_CONFIG, "TN_MLP_LEAN: weights do not fit LDS");
+    return TN_OK;
+}
+
+extern "C" __attribute__((visibility("hidden"))) int tn_mlp_wgrad_lean_check(const tn_mlp_desc *desc, const tn_mlp_desc *partner, const float *x,
+                                                                             const float *aux, int64_t n, float *const *gw, float *const *gb,
+                                                                             float *const *gws, float *const *gbs, const float *ws_a,
+                                                                             const float *ws_b)
+{
+    RcArgs p;
+    return lean_plan(p, desc, partner, x, aux, n, gw, gb, gws, gbs, ws_a, ws_b);
+}
+
+// Weight / bias gradients of the paired heads under TN_MLP_LEAN: `desc` = the 5-layer head (TN_ENC_AUX_CAT on 96 inputs), `partner` = the
+// 2-layer head on the same x; workspaces as the chain half of tn_mlp_bwd_pair left them.  Gradients accumulate (+=).
 extern "C" int tn_mlp_wgrad_lean_pair(const tn_mlp_desc *desc, const tn_mlp_desc *partner, const float *x, const float *aux, int64_t n,
                                       float *const *gw, float *const *gb, float *const *gws, float *const *gbs, const float *ws_a,
                                       const float *ws_b, void *stream)
 {
-    TN_REQUIRE(desc && partner && x && gw && gb && gws && gbs && ws_a && ws_b, TN_E_NULL, "tn_mlp_wgrad_lean_pair: null pointer");
     RcArgs p;
-    int Ha = 0, Hb = 0;
-    if (int rc = plan(desc, p.a, Ha)) return rc;
-    if (int rc = plan(partner, p.b, Hb)) return rc;
-    TN_REQUIRE(Ha == 64 && Hb == 64 && p.a.n_layers == 5 && p.b.n_layers == 2 && p.a.in_dim == 96 && p.b.in_dim == 96 && p.a.out_dim <= 4 &&
-                   p.b.out_dim <= 4 && p.a.enc == TN_ENC_AUX_CAT && p.b.enc == TN_ENC_NONE && p.a.f2 && p.b.f2 &&
-                   f2_head_ok(p.a, 64) && f2_head_ok(p.b, 64) && p.a.out_dim == 3 && p.b.out_dim == 1 && p.a.K0_pad - p.a.in_dim == 56,
-               TN_E_CONFIG, "TN_MLP_LEAN: the reference's decoders (run.py:133-139) as f16x2 heads (TN_MLP_F16X2): colour 147 -> 64 x 4 -> 3 on "
-                            "[per-ray table (51), x (96)], sigma 96 -> 64 -> 1");
-    TN_REQUIRE(aux && ((uintptr_t)aux & 15) == 0 && p.a.aux_index, TN_E_NULL, "TN_MLP_LEAN: aux table (16-byte aligned) and aux_index are required");
-    TN_REQUIRE((((uintptr_t)x | (uintptr_t)ws_a | (uintptr_t)ws_b) & 15) == 0, TN_E_ALIGN, "TN_MLP_LEAN: x / workspaces must be 16-byte aligned");
+    if (int rc = lean_plan(p, desc, partner, x, aux, n, gw, gb, gws, gbs, ws_a, ws_b)) return rc;
     if (n <= 0) return TN_OK;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t n_tiles = (n + 31) / 32;
     // ---- first layers ----
-    {
-        FlArgs f;
-        f.x = x; f.aux = aux; f.aux_index = p.a.aux_index; f.aux_stride = p.a.aux_stride;
-        f.pe = p.a.K0 - p.a.in_dim;
-        f.ws_a = ws_a; f.ws_b = ws_b;
-        f.rt_a = stash_rows(H, NH, 0); f.rt_b = stash_rows(H, 1, 0);
-        f.g0_a = NH * H; f.g0_b = H;
-        f.K0_a = p.a.K0; f.K0_b = p.b.K0;
-        f.gW0 = gw[0]; f.gB0 = gb[0]; f.gW0s = gws[0]; f.gB0s = gbs[0];
-        f.n = n;
-        TN_REQUIRE(f.gW0 && f.gB0 && f.gW0s && f.gB0s, TN_E_NULL, "TN_MLP_LEAN: null gradient pointer");
-        TN_REQUIRE(f.aux_stride >= FL_AW && f.pe <= FL_AW, TN_E_CONFIG, "TN_MLP_LEAN: table rows of 56 .. floats, at most 56 columns in use");
-        const size_t lds1 = (2 * (size_t)FL_BUF + 16) * 4;
-        hipError_t e1 = hipFuncSetAttribute((const void *)wgrad_first_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1);
-        if (e1 != hipSuccess) { tn::set_error("TN_MLP_LEAN: cannot reserve %zu B of LDS: %s", lds1, hipGetErrorString(e1)); return (int)e1; }
-        const int64_t blocks = std::min<int64_t>(n_tiles, 256 * 2);
-        wgrad_first_kernel<<<dim3((unsigned)blocks), dim3(512), lds1, s>>>(f);
-        if (int rc = tn::check_launch("wgrad_first_kernel")) return rc;
-    }
+    FlArgs f;
+    f.x = x; f.aux = aux; f.aux_index = p.a.aux_index; f.aux_stride = p.a.aux_stride;
+    f.pe = p.a.K0 - p.a.in_dim;
+    f.ws_a = ws_a; f.ws_b = ws_b;
+    f.rt_a = stash_rows(H, NH, 0); f.rt_b = stash_rows(H, 1, 0);
+    f.g0_a = NH * H; f.g0_b = H;
+    f.K0_a = p.a.K0; f.K0_b = p.b.K0;
+    f.gW0 = gw[0]; f.gB0 = gb[0]; f.gW0s = gws[0]; f.gB0s = gbs[0];
+    f.n = n;
+    const size_t lds1 = (2 * (size_t)FL_BUF + 16) * 4;
+    if (int rc = launch(wgrad_first_kernel, 8, lds1, grid_blocks(n, 1, 256 * 2), s, "wgrad_first_kernel", f)) return rc;
     // ---- hidden and output layers, activations rebuilt ----
-    plan_f2(p.a, 64);
-    plan_f2(p.b, 64);
     p.x = x; p.aux = aux; p.ws_a = ws_a; p.ws_b = ws_b; p.n = n;
-    for (int l = 0; l < 5; ++l) { p.gW[l] = gw[l]; p.gB[l] = gb[l]; TN_REQUIRE(gw[l] && gb[l], TN_E_NULL, "TN_MLP_LEAN: null gradient pointer"); }
+    for (int l = 0; l < 5; ++l) { p.gW[l] = gw[l]; p.gB[l] = gb[l]; }
     p.gWs = gws[1]; p.gBs = gbs[1];
-    TN_REQUIRE(p.gWs && p.gBs, TN_E_NULL, "TN_MLP_LEAN: null gradient pointer");
     constexpr int WPB = 4;                    // one wave per SIMD: 192 accumulator registers per wave
     const size_t lds_bytes = ((size_t)p.a.lds_floats + (size_t)p.b.lds_floats) * 4;
-    TN_REQUIRE(lds_bytes <= (size_t)LDS_LIMIT_BYTES, TN_E_CONFIG, "TN_MLP_LEAN: weights do not fit LDS");
-    auto kern = wgrad_rc_kernel<WPB, true, 3, 1, 7, 4>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("TN_MLP_LEAN: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t blocks = std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256);
-    kern<<<dim3((unsigned)blocks), dim3(WPB * 64), lds_bytes, s>>>(p);
-    return tn::check_launch("wgrad_rc_kernel");
+    return launch(wgrad_rc_kernel<WPB, true, 3, 1, 7, 4>, WPB, lds_bytes, grid_blocks(n, WPB, 256), s, "wgrad_rc_kernel", p);
 }
