@@ -13,8 +13,9 @@ gradient buffers allocated), which saves two passes over the 126 MiB of plane gr
 from __future__ import annotations
 
 import ctypes as C
-import os
-from typing import Any, List, Optional, Sequence
+import enum
+from dataclasses import dataclass
+from typing import Any, Callable, List, Optional, Sequence, Tuple
 
 import torch
 from torch.autograd import Function
@@ -35,11 +36,9 @@ def MATMUL_F16X2() -> bool:
     return ROWS_HANDOFF and models.MATMUL == "f16x2"
 
 
-PAIR_FORWARD = True       # both heads' training forwards in one launch (tn_mlp_fwd_stash_pair)
-FUSE_GATHER = True        # ... with the K-Planes gather inside that launch (tn_kplanes_mlp_fwd_pair)
+FUSE_GATHER = True        # the K-Planes gather inside the heads' forward launch (tn_kplanes_mlp_fwd_pair, tn_kplanes_mlp_fwd)
 FUSE_SCATTER = True       # backward: the plane scatter inside the data-gradient chain launch (tn_kplanes_mlp_bwd_pair)
-PAIR_BACKWARD = True      # both heads' data gradients in one launch (tn_mlp_bwd_pair); False: one tn_mlp_bwd per head
-# ... also behind the wide stacks (_RenderHeads; round 5): tn_mlp_bwd_pair takes both heads' first-layer weight gradients over the x
+# behind the wide stacks (_RenderHeads; round 5): tn_mlp_bwd_pair takes both heads' first-layer weight gradients over the x
 # columns in ONE launch (x rows read once) and, where both first layers fit LDS (128-wide stack), both data gradients in one pass; "0": off
 HEADS_PAIR_BACKWARD = CONFIG.heads_pair
 # round 5 (TN_MLP_SKIP_LAST): behind a wide stack whose last layer is a plain Linear (Vanilla 256 -> 256, Cobafa 128 -> 128: reference
@@ -51,14 +50,6 @@ MERGE_LAST = CONFIG.merge_last
 # rebuild the hidden activations from the feature rows (csrc/mlp_wgrad_rc.hip) -- 2.7 GB less workspace traffic per K-Planes step.
 # TN_KP_LEAN=0: the stash-everything form of rounds 1-4 (A/B runs; always taken by the fp32 / bf16x3 head forms)
 KP_LEAN = CONFIG.kp_lean
-_side_streams: dict = {}
-
-
-def _side_stream(dev: torch.device) -> "torch.cuda.Stream":
-    s = _side_streams.get(dev)
-    if s is None:
-        s = _side_streams[dev] = torch.cuda.Stream(dev)
-    return s
 
 
 def _alloc(arena: Optional[Arena], name: str, shape, dev: torch.device, dtype=torch.float32) -> torch.Tensor:
@@ -74,16 +65,21 @@ def _workspace(desc: L.MlpDesc, n: int, dev: torch.device, arena: Optional[Arena
     return _alloc(arena, name, (nbytes // 4,), dev), nbytes
 
 
+def _covered(hint: Optional[dict], packed: torch.Tensor, R: int) -> bool:
+    """the trainer's sampler wrote ray ids, steps and ray directions for exactly this batch and covers every sample"""
+    return hint is not None and hint.get("key") == (packed.data_ptr(), packed.size(0), R)
+
+
 def _ray_aux(packed: torch.Tensor, info: torch.Tensor, freqs: torch.Tensor, n_freqs: int, arena: Optional[Arena], hint: Optional[dict]):
     """Per-ray inputs of the colour head (models.py:87: cat[PE(d), d]): evaluated once per ray into a table
     (tn_dir_encode) that the MLP kernels index through the ray id of every sample, instead of 48 sin/cos per sample.
-    Returns (table, ray_ids, stride, steps).  ``hint``: ray ids / steps / ray directions the sampler already wrote out
+    Returns (table, ray_ids, steps).  ``hint``: ray ids / steps / ray directions the sampler already wrote out
     for exactly this batch (run.Trainer.build_batch); otherwise they are rebuilt from (packed, info)."""
     dev = packed.device
     n, R = packed.size(0), info.size(0)
     stride = (6 * n_freqs + 3 + 7) & ~7
     table = _alloc(arena, "aux_table", (R, stride), dev)
-    if hint is not None and hint.get("key") == (packed.data_ptr(), n, R):
+    if _covered(hint, packed, R):
         ray_ids, steps, dirs_ray = hint["ray_ids"], hint["steps"], hint["dirs"]
     else:
         ray_ids = _alloc(arena, "ray_ids", (n,), dev, torch.int32)
@@ -92,7 +88,7 @@ def _ray_aux(packed: torch.Tensor, info: torch.Tensor, freqs: torch.Tensor, n_fr
         L.call("tn_ray_aux", dev, L.ptr(packed), L.ptr(info), C.c_int64(R), L.ptr(ray_ids), L.ptr(steps), L.ptr(dirs_ray))
     if n > 0:
         L.call("tn_dir_encode", dev, L.ptr(dirs_ray), C.c_int64(R), L.ptr(freqs), C.c_int(n_freqs), L.ptr(table), C.c_int(stride))
-    return table, ray_ids, stride, steps
+    return table, ray_ids, steps
 
 
 def _gate_slot(hint: Optional[dict], wanted: bool) -> Optional[torch.Tensor]:
@@ -105,13 +101,6 @@ def _gate_slot(hint: Optional[dict], wanted: bool) -> Optional[torch.Tensor]:
         hint["gate"].zero_()
     hint["gate_used"] = True
     return hint["gate"]
-
-
-def _upstream_is_gated(ctx: Any) -> bool:
-    """The node's backward applies the gate itself unless the caller has DECLARED the upstream gradient gated
-    (run.Trainer.step_on_batch sets stats["upstream_gated"] around tn_mse_grad_gated): any other loss on a trainer-built batch
-    -- a test, a custom loop -- then still gets the reference's zero gradients in an all-masked step (core.py:251-254)"""
-    return bool(ctx.gate_in_slot and ctx.stats is not None and ctx.stats.get("upstream_gated"))
 
 
 INFER_PAIR = CONFIG.infer_pair       # (TN_INFER_PAIR=0: always the gated inference form -- A/B, debugging)
@@ -159,219 +148,314 @@ def _note_live_fraction(stats: dict, weights: torch.Tensor) -> None:
     # every slot still in flight: skip this measurement
 
 
+@dataclass
+class _Call:
+    """A render node's inputs that are not tensors (render())."""
+    thr: float
+    n_freqs: int
+    n_planes: int               # the parameters: K-Planes' planes (none for _RenderHeads), the sigma head's, the colour head's
+    n_sigma: int
+    accumulate: bool            # weight gradients go straight into param.grad where it exists (the trainer keeps it allocated)
+    arena: Optional[Arena]
+    train: bool
+    hint: Optional[dict]        # run.Trainer.build_batch's _batch_aux
+    stats: Optional[dict]       # the renderer's _stats
+    link: Optional[dict] = None     # _RenderHeads: row views offered by the wide stack that produced feat
+
+    def split(self, params: Sequence[torch.Tensor]) -> Tuple[List[torch.Tensor], List[torch.Tensor], List[torch.Tensor]]:
+        k = self.n_planes + self.n_sigma
+        return list(params[:self.n_planes]), [p.contiguous() for p in params[self.n_planes:k]], [p.contiguous() for p in params[k:]]
+
+
+# eligibility rules of the paired and fused launch forms, each written once
+def _heads64(sig_p: Sequence[torch.Tensor], rgb_p: Sequence[torch.Tensor]) -> bool:
+    """both heads 64 wide: the width of every paired head launch"""
+    return sig_p[0].size(0) == 64 and rgb_p[0].size(0) == 64
+
+
+def _planes_3x32(kdesc: L.KPlanesDesc, keep: Sequence[torch.Tensor]) -> bool:
+    """the plane set the fused gather and scatter take: 3 scales x 32 channels, all nine planes present"""
+    return kdesc.n_scales == 3 and kdesc.channels == 32 and len(keep) == 9
+
+
+def _stack_pair_bwd(F: int, sig_p: Sequence[torch.Tensor], rgb_p: Sequence[torch.Tensor]) -> bool:
+    """behind a wide stack: both heads' backward in one tn_mlp_bwd_pair"""
+    return F % 64 == 0 and len(sig_p) // 2 == 2 and len(rgb_p) // 2 == 5 and _heads64(sig_p, rgb_p)
+
+
+class _KpFwd(enum.Enum):
+    INFER_PAIR = "gather + both heads of every sample in one launch, nothing stashed (tn_kplanes_mlp_fwd_pair)"
+    INFER_GATHER_SIGMA = "gather + sigma head in one launch (tn_kplanes_mlp_fwd), the colour head gated by the weights"
+    INFER_PLAIN = "tn_kplanes_fwd, the sigma head, the colour head gated by the weights"
+    TRAIN_GATHER_PAIR = "gather + both heads in one launch, stashed (tn_kplanes_mlp_fwd_pair)"
+    TRAIN_PAIR = "tn_kplanes_fwd, then both heads in one launch (tn_mlp_fwd_stash_pair)"
+    TRAIN_STASH = "tn_kplanes_fwd, then each head on its own, stashed where it has a workspace"
+
+
+class _KpBwd(enum.Enum):
+    SCATTER_CHAIN = "tn_kplanes_mlp_bwd_pair: data gradients + plane scatter, [planes_ready], then the weight gradients"
+    PAIR_SPLIT = "tn_mlp_bwd_pair data gradients, tn_kplanes_bwd, planes_ready, tn_mlp_bwd_pair weight gradients"
+    PAIR = "tn_mlp_bwd_pair, then tn_kplanes_bwd"
+    SEPARATE = "one tn_mlp_bwd per head, then tn_kplanes_bwd"
+
+
+@dataclass(frozen=True)
+class _KPlanesPlan:
+    fwd: _KpFwd
+    bwd: Optional[_KpBwd]       # None: inference
+    lean: bool                  # TN_MLP_LEAN on both heads: no hidden activations stashed, the weight-gradient launches rebuild them
+    note_live: bool             # measure the live fraction for the next inference call's form
+    covered: bool
+    sb: int                     # workspace bytes of the sigma and the colour head (0: none)
+    rb: int
+
+    @property
+    def rays_fwd(self) -> bool:
+        """both heads are done before the weights: weights and composite as one launch per ray (tn_render_rays_fwd)"""
+        return self.fwd in (_KpFwd.INFER_PAIR, _KpFwd.TRAIN_GATHER_PAIR, _KpFwd.TRAIN_PAIR)
+
+    @property
+    def flags(self) -> int:
+        return L.MLP_LEAN if self.lean else 0
+
+
+def _plan_kplanes(kdesc, keep, rdesc, sdesc, sig_p, rgb_p, train: bool, sb: int, rb: int, covered: bool, planes_ready: bool,
+                  stats: Optional[dict]) -> _KPlanesPlan:
+    F = kdesc.n_scales * kdesc.channels
+    planes = _planes_3x32(kdesc, keep)
+    pair_fwd = bool(sb and rb) and F % 4 == 0 and _heads64(sig_p, rgb_p)
+    pair_bwd = bool(sb and rb) and F % 32 == 0 and len(sig_p) // 2 == 2 and _heads64(sig_p, rgb_p)
+    # TN_MLP_LEAN: only the paired backward rebuilds the hidden activations (csrc/mlp_wgrad_rc.hip)
+    lean = pair_fwd and pair_bwd and KP_LEAN and bool(L.lib().tn_mlp_lean_supported(C.byref(rdesc), C.byref(sdesc)))
+    gather_sigma = not train and FUSE_GATHER and F % 4 == 0 and sig_p[0].size(0) == 64 and planes
+    bwd = None
+    if train:
+        fwd = _KpFwd.TRAIN_GATHER_PAIR if pair_fwd and FUSE_GATHER and planes else _KpFwd.TRAIN_PAIR if pair_fwd else _KpFwd.TRAIN_STASH
+        if not pair_bwd:
+            bwd = _KpBwd.SEPARATE
+        elif FUSE_SCATTER and planes:
+            bwd = _KpBwd.SCATTER_CHAIN
+        else:       # N > 1: the plane gradients go on the wire between the data and the weight gradients
+            bwd = _KpBwd.PAIR_SPLIT if planes_ready else _KpBwd.PAIR
+    # inference, two forms with identical results (a sample with w == 0 contributes exactly 0 either way, core.py:243-249):
+    #   gated: gather + sigma head -> weights -> colour head on the 32-sample tiles that hold a weight -> composite;
+    #   pair:  gather + BOTH heads of every sample in one launch (no feature rows, nothing stashed) -> weights + composite.
+    # The pair wins while most tiles are alive (an untrained or half-trained field: 0.6 against 0.9 ms per 2^20 samples), the
+    # gated form once early termination has emptied most of them; the choice follows the live fraction of the previous call
+    elif gather_sigma and INFER_PAIR and rgb_p[0].size(0) == 64 and len(rgb_p) == 10 and _infer_prefers_pair(stats):
+        fwd = _KpFwd.INFER_PAIR
+    else:
+        fwd = _KpFwd.INFER_GATHER_SIGMA if gather_sigma else _KpFwd.INFER_PLAIN
+    return _KPlanesPlan(fwd, bwd, lean, gather_sigma and INFER_PAIR and stats is not None, covered, sb, rb)
+
+
+@dataclass(frozen=True)
+class _HeadsPlan:
+    rows_fwd: bool              # the heads' forwards read x from the wide stack's workspace rows (f16x2 heads) ...
+    x_from_rows: bool           # ... and only there: the stack wrote no row-major copy (TN_MLP_ROWS_ONLY)
+    pair_bwd: bool              # both heads' backward in one tn_mlp_bwd_pair
+    covered: bool
+    sb: int
+    rb: int
+
+
+def _plan_heads(F: int, sig_p, rgb_p, train: bool, link: Optional[dict], sb: int, rb: int, covered: bool) -> _HeadsPlan:
+    if train and not (sb and rb):
+        raise RuntimeError("tinynerf_amd: these decoder shapes are outside the fused render node (use renderer.fused = False)")
+    # f16x2 heads read their first-layer operands from the stack's row view (128-byte rows instead of 16 bytes per lane and
+    # sample); once a forward has done so the stack stops writing the row-major feat (TN_MLP_ROWS_ONLY / TN_MLP_X_FROM_ROWS)
+    rows_fwd = link is not None and MATMUL_F16X2()
+    pair_bwd = link is not None and HEADS_PAIR_BACKWARD and _stack_pair_bwd(F, sig_p, rgb_p)
+    return _HeadsPlan(rows_fwd, rows_fwd and bool(link.get("rows_only")), pair_bwd, covered, sb, rb)
+
+
+def _head_descs(sig_p, rgb_p, F: int, n_freqs: int, freqs, ray_ids, table, rflags: int = 0, sflags: int = 0) -> Tuple[L.MlpDesc, L.MlpDesc]:
+    """the colour and the sigma head.  The colour head's input is cat[PE(d), d, x] (models.py:87): PE(d) from the per-ray table
+    through the ray id of every sample where there is one (TN_ENC_AUX_CAT), otherwise evaluated per sample (TN_ENC_DIR_CAT)"""
+    enc, stride = (L.ENC_AUX_CAT, table.size(1)) if ray_ids is not None else (L.ENC_DIR_CAT, 0)
+    rdesc = _mlp_desc(rgb_p, F, enc, n_freqs, L.ACT_SIGMOID, freqs, rflags, ray_ids, stride)
+    sdesc = _mlp_desc(sig_p, F, L.ENC_NONE, 0, L.ACT_EXP_M1, None, sflags)
+    return rdesc, sdesc
+
+
+def _head_fwd(dev: torch.device, desc: L.MlpDesc, x, aux, n: int, y, ws, nbytes: int, gate: Optional[torch.Tensor] = None) -> None:
+    """one head's forward: stashed for the backward where it has a workspace; otherwise only on the 32-sample tiles where
+    `gate` (the weights) is not 0 (core.py:246-251)"""
+    if ws is not None:
+        L.call("tn_mlp_fwd_stash", dev, C.byref(desc), L.ptr(x), L.ptr(aux), C.c_int64(n), L.ptr(y), L.ptr(ws), C.c_int64(nbytes))
+        return
+    desc.row_gate = None if gate is None else gate.data_ptr()
+    L.call("tn_mlp_fwd", dev, C.byref(desc), L.ptr(x), L.ptr(aux), C.c_int64(n), L.ptr(y), C.c_void_p(None))
+    desc.row_gate = None
+
+
+def _composite(ctx: Any, a: _Call, covered: bool, dev: torch.device, sigma, steps, rgbs, info, bg, colour: Optional[Callable], rays: bool):
+    """weights scan and composite behind the sigma head, -> (out, weights).  `rays`: `colour(weights)` if given, then weights and
+    composite as one launch per ray (tn_render_rays_fwd, bit-identical to the two); otherwise weights -> colour(weights) -> composite"""
+    n, R = sigma.size(0), info.size(0)
+    weights = _alloc(a.arena, "weights", (n,), dev)
+    if not covered:
+        weights.zero_()          # cuda.cu:84 (zeros_like): samples outside every (start, count) keep weight 0
+    # harness: a zeroed [1] slot that the weights kernel raises when any weight is > 0 (instead of a reduction launch), and an
+    # upstream gradient that arrives gated (tn_mse_grad_gated) -- see the "Empty iteration" note below
+    gate_slot = _gate_slot(a.hint, covered and a.train)
+    out = torch.empty((R, 3), device=dev)
+    if rays:
+        if colour is not None:
+            colour(weights)
+        L.call("tn_render_rays_fwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), C.c_float(a.thr), L.ptr(weights),
+               L.ptr(out), L.ptr(gate_slot), C.c_int64(n), C.c_int64(R))
+    else:
+        gate = (L.ptr(gate_slot),) if gate_slot is not None else ()
+        L.call("tn_weights_fwd_gate" if gate else "tn_weights_fwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(info), C.c_float(a.thr),
+               L.ptr(weights), *gate, C.c_int64(n), C.c_int64(R))
+        colour(weights)
+        L.call("tn_composite_fwd", dev, L.ptr(rgbs), L.ptr(weights), L.ptr(info), L.ptr(bg), L.ptr(out), C.c_void_p(None),
+               C.c_int64(n), C.c_int64(R))
+    # core.py:246-254: when EVERY sample is masked (w == 0 everywhere) the reference renders the background from constants
+    # that carry no graph, i.e. no parameter receives a gradient from the image loss; here the upstream gradient is gated
+    # (a [1] tensor kept outside save_for_backward: with N > 1 the trainer all-reduces it in place right after this forward
+    # (run.Trainer.step_on_batch) -- the single-GPU step on the union of the ranks' rays is only "empty" when every
+    # rank's is -- so the backward already reads the all-rank value)
+    ctx.gate_in_slot, ctx.stats = gate_slot is not None, a.stats
+    ctx.gate = gate_slot if gate_slot is not None else (weights.amax().reshape(1) if a.train else None)
+    if a.stats is not None:
+        a.stats["gate"] = ctx.gate
+        a.stats["pre_gated"] = ctx.gate_in_slot        # the caller MAY hand in a gated gradient (and must then say so)
+        a.stats["upstream_gated"] = False
+        if a.stats.get("maps_handout") is not None:   # NerfRenderer.render_maps: the weights this forward composited with
+            a.stats["maps_handout"]["weights"] = weights
+    return out, weights
+
+
+def _grad_buffers(ctx: Any, params: Sequence[torch.Tensor]) -> Tuple[List[torch.Tensor], List[Optional[torch.Tensor]]]:
+    """where the kernels write each parameter's gradient -- param.grad itself when the caller accumulates into it and it has the
+    parameter's layout, a zeroed tensor otherwise -- and what the backward returns to autograd (None for the former)"""
+    refs: Sequence[Optional[torch.Tensor]] = ctx.param_refs if ctx.param_refs is not None else [None] * len(params)
+    in_place = [r is not None and r.is_leaf and r.grad is not None and r.grad.stride() == p.stride() for p, r in zip(params, refs)]
+    bufs = [r.grad if ip else torch.zeros_like(p) for p, r, ip in zip(params, refs, in_place)]
+    return bufs, [None if ip else g for g, ip in zip(bufs, in_place)]
+
+
+def _grad_ptrs(g_sig: Sequence[torch.Tensor], g_rgb: Sequence[torch.Tensor]):
+    """the heads' weight and bias gradient pointers, in the kernels' argument order (gw_r, gb_r, gw_s, gb_s)"""
+    return tuple((C.c_void_p * len(gs))(*[g.data_ptr() for g in gs]) for gs in (g_rgb[0::2], g_rgb[1::2], g_sig[0::2], g_sig[1::2]))
+
+
+def _heads_bwd(dev: torch.device, pair: bool, rdesc, sdesc, feat, table, g_rgbs, g_sigma, gw, g_feat, ws_r, rb: int, ws_s, sb: int):
+    """both heads' backward: one tn_mlp_bwd_pair, or one tn_mlp_bwd per head"""
+    n = C.c_int64(feat.size(0))
+    if pair:
+        L.call("tn_mlp_bwd_pair", dev, C.byref(rdesc), C.byref(sdesc), L.ptr(feat), L.ptr(table), L.ptr(g_rgbs), L.ptr(g_sigma), n, *gw,
+               L.ptr(g_feat), L.ptr(ws_r), C.c_int64(rb), L.ptr(ws_s), C.c_int64(sb))
+        return
+    L.call("tn_mlp_bwd", dev, C.byref(rdesc), L.ptr(feat), L.ptr(table), L.ptr(g_rgbs), n, *gw[:2], L.ptr(g_feat), L.ptr(ws_r), C.c_int64(rb))
+    L.call("tn_mlp_bwd", dev, C.byref(sdesc), L.ptr(feat), C.c_void_p(None), L.ptr(g_sigma), n, *gw[2:], L.ptr(g_feat), L.ptr(ws_s), C.c_int64(sb))
+
+
+def _rays_bwd(ctx: Any, grad_out: torch.Tensor, sigma, steps, rgbs, info, bg, weights) -> Tuple[torch.Tensor, torch.Tensor]:
+    """composite -> (rgbs, weights) and weights -> sigma as one launch per ray (the weights' gradient needs only the composite's)"""
+    g_out = grad_out.contiguous()
+    # "Empty iteration": zero gradients, as on the module-by-module path.  Applied here unless the caller has DECLARED the upstream
+    # gradient gated (run.Trainer.step_on_batch sets stats["upstream_gated"] around tn_mse_grad_gated): any other loss on a
+    # trainer-built batch -- a test, a custom loop -- then still gets the reference's zero gradients in an all-masked step (core.py:251-254)
+    if ctx.gate is not None and not (ctx.gate_in_slot and ctx.stats is not None and ctx.stats.get("upstream_gated")):
+        g_out = g_out * (ctx.gate > 0).to(g_out.dtype)
+    dev, n, R = sigma.device, sigma.size(0), info.size(0)
+    g_rgbs = _alloc(ctx.call.arena, "g_rgbs", (n, 3), dev)
+    g_sigma = _alloc(ctx.call.arena, "g_sigma", (n,), dev)
+    if not ctx.plan.covered:     # samples no ray owns: zero gradient, not whatever the arena held (the kernel writes every
+        g_rgbs.zero_(); g_sigma.zero_()      # sample a ray owns)
+    L.call("tn_render_rays_bwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), L.ptr(weights),
+           L.ptr(g_out), L.ptr(g_rgbs), L.ptr(g_sigma), C.c_int64(n), C.c_int64(R))
+    return g_rgbs, g_sigma
+
+
 class _RenderKPlanes(Function):
     @staticmethod
-    def forward(ctx: Any, packed: torch.Tensor, info: torch.Tensor, bg: Optional[torch.Tensor], thr: float,
-                freqs: torch.Tensor, n_freqs: int, n_planes: int, n_sigma: int, accumulate: bool, arena: Optional[Arena],
-                train: bool, hint: Optional[dict], stats: Optional[dict], *params: torch.Tensor) -> torch.Tensor:  # type: ignore
-        planes = list(params[:n_planes])
-        sig_p = [p.contiguous() for p in params[n_planes:n_planes + n_sigma]]
-        rgb_p = [p.contiguous() for p in params[n_planes + n_sigma:]]
+    def forward(ctx: Any, a: _Call, packed: torch.Tensor, info: torch.Tensor, bg: Optional[torch.Tensor], freqs: torch.Tensor,
+                *params: torch.Tensor) -> torch.Tensor:  # type: ignore
+        planes, sig_p, rgb_p = a.split(params)
         dev = L.require_cuda(packed, info, *sig_p, *rgb_p)
         n, R = packed.size(0), info.size(0)
         kdesc, keep = _kplanes_desc(planes)
         F = kdesc.n_scales * kdesc.channels
-        feat = _alloc(arena, "feat", (n, F), dev)
-        table, ray_ids, stride, steps = _ray_aux(packed, info, freqs, n_freqs, arena, hint)
-        sdesc = _mlp_desc(sig_p, F, L.ENC_NONE, 0, L.ACT_EXP_M1, None)
-        rdesc = _mlp_desc(rgb_p, F, L.ENC_AUX_CAT, n_freqs, L.ACT_SIGMOID, freqs, 0, ray_ids, stride)
-        ws_s = ws_r = None
-        sb = rb = 0
-        if train:          # training forward: activations go to the backward's workspace, nothing is recomputed
-            ws_s, sb = _workspace(sdesc, n, dev, arena, "ws_sigma")
-            ws_r, rb = _workspace(rdesc, n, dev, arena, "ws_rgb")
-        sigma = _alloc(arena, "sigma", (n,), dev)
-        rgbs = _alloc(arena, "rgbs", (n, 3), dev)
-        pair = (ws_s is not None and ws_r is not None and PAIR_FORWARD and F % 4 == 0 and sig_p[0].size(0) == 64 and rgb_p[0].size(0) == 64)
-        # TN_MLP_LEAN: no hidden activations in the workspace, the weight-gradient launches rebuild them (csrc/mlp_wgrad_rc.hip)
-        lean = bool(pair and KP_LEAN and PAIR_BACKWARD and L.lib().tn_mlp_lean_supported(C.byref(rdesc), C.byref(sdesc)))
-        if lean:
-            rdesc.flags |= L.MLP_LEAN
-            sdesc.flags |= L.MLP_LEAN
-        gather_fused = pair and FUSE_GATHER and kdesc.n_scales == 3 and kdesc.channels == 32 and len(keep) == 9
-        gather_sigma = (not train and FUSE_GATHER and F % 4 == 0 and sig_p[0].size(0) == 64 and kdesc.n_scales == 3 and kdesc.channels == 32
-                        and len(keep) == 9)
-        # inference, two forms with identical results (a sample with w == 0 contributes exactly 0 either way, core.py:243-249):
-        #   gated: gather + sigma head -> weights -> colour head on the 32-sample tiles that hold a weight -> composite;
-        #   pair:  gather + BOTH heads of every sample in one launch (no feature rows, nothing stashed) -> weights + composite.
-        # The pair wins while most tiles are alive (an untrained or half-trained field: 0.6 against 0.9 ms per 2^20 samples), the
-        # gated form once early termination has emptied most of them; the choice follows the live fraction of the previous call
-        infer_pair = gather_sigma and INFER_PAIR and rgb_p[0].size(0) == 64 and len(rgb_p) == 10 and _infer_prefers_pair(stats)
-        if infer_pair:
-            L.call("tn_kplanes_mlp_fwd_pair", dev, C.byref(kdesc), L.ptr(packed), C.c_int64(7), C.byref(rdesc), C.byref(sdesc), L.ptr(table),
-                   C.c_int64(n), L.ptr(feat), L.ptr(rgbs), L.ptr(sigma), C.c_void_p(None), C.c_int64(0), C.c_void_p(None), C.c_int64(0))
-        elif gather_sigma:   # inference: gather + sigma head in one launch
-            L.call("tn_kplanes_mlp_fwd", dev, C.byref(kdesc), L.ptr(packed), C.c_int64(7), C.byref(sdesc), C.c_int64(n), L.ptr(feat), L.ptr(sigma))
-        elif gather_fused:   # gather + both heads in ONE launch: the feature rows go from the texel lines to the MFMA operands
-            L.call("tn_kplanes_mlp_fwd_pair", dev, C.byref(kdesc), L.ptr(packed), C.c_int64(7), C.byref(rdesc), C.byref(sdesc), L.ptr(table),
-                   C.c_int64(n), L.ptr(feat), L.ptr(rgbs), L.ptr(sigma), L.ptr(ws_r), C.c_int64(rb), L.ptr(ws_s), C.c_int64(sb))
-        else:
-            L.call("tn_kplanes_fwd", dev, C.byref(kdesc), L.ptr(packed), C.c_int64(7), C.c_int64(n), L.ptr(feat))
-        if gather_fused or gather_sigma:
-            pass
-        elif pair:         # both heads in one launch: the feature rows are read from HBM once
-            L.call("tn_mlp_fwd_stash_pair", dev, C.byref(rdesc), C.byref(sdesc), L.ptr(feat), L.ptr(table), C.c_int64(n), L.ptr(rgbs),
+        feat = _alloc(a.arena, "feat", (n, F), dev)
+        table, ray_ids, steps = _ray_aux(packed, info, freqs, a.n_freqs, a.arena, a.hint)
+        rdesc, sdesc = _head_descs(sig_p, rgb_p, F, a.n_freqs, freqs, ray_ids, table)
+        # training forward: activations go to the backward's workspace, nothing is recomputed
+        ws_s, sb = _workspace(sdesc, n, dev, a.arena, "ws_sigma") if a.train else (None, 0)
+        ws_r, rb = _workspace(rdesc, n, dev, a.arena, "ws_rgb") if a.train else (None, 0)
+        ready = a.hint.get("planes_ready") if (a.hint is not None and a.accumulate) else None
+        p = _plan_kplanes(kdesc, keep, rdesc, sdesc, sig_p, rgb_p, a.train, sb, rb, _covered(a.hint, packed, R), ready is not None,
+                          a.stats)
+        rdesc.flags, sdesc.flags = rdesc.flags | p.flags, sdesc.flags | p.flags
+        sigma = _alloc(a.arena, "sigma", (n,), dev)
+        rgbs = _alloc(a.arena, "rgbs", (n, 3), dev)
+        kp = (C.byref(kdesc), L.ptr(packed), C.c_int64(7))
+        if p.fwd in (_KpFwd.INFER_PAIR, _KpFwd.TRAIN_GATHER_PAIR):
+            # the feature rows go from the texel lines to the MFMA operands
+            L.call("tn_kplanes_mlp_fwd_pair", dev, *kp, C.byref(rdesc), C.byref(sdesc), L.ptr(table), C.c_int64(n), L.ptr(feat), L.ptr(rgbs),
                    L.ptr(sigma), L.ptr(ws_r), C.c_int64(rb), L.ptr(ws_s), C.c_int64(sb))
-        elif ws_s is not None:
-            L.call("tn_mlp_fwd_stash", dev, C.byref(sdesc), L.ptr(feat), C.c_void_p(None), C.c_int64(n), L.ptr(sigma), L.ptr(ws_s), C.c_int64(sb))
+        elif p.fwd is _KpFwd.INFER_GATHER_SIGMA:
+            L.call("tn_kplanes_mlp_fwd", dev, *kp, C.byref(sdesc), C.c_int64(n), L.ptr(feat), L.ptr(sigma))
         else:
-            L.call("tn_mlp_fwd", dev, C.byref(sdesc), L.ptr(feat), C.c_void_p(None), C.c_int64(n), L.ptr(sigma), C.c_void_p(None))
-        weights = _alloc(arena, "weights", (n,), dev)
-        covered = hint is not None and hint.get("key") == (packed.data_ptr(), n, R)     # the trainer's sampler covers every sample
-        if not covered:
-            weights.zero_()          # cuda.cu:84 (zeros_like): samples outside every (start, count) keep weight 0
-        # harness: a zeroed [1] slot that the weights kernel raises when any weight is > 0 (instead of a reduction launch), and an
-        # upstream gradient that arrives gated (tn_mse_grad_gated) -- see the "Empty iteration" note below
-        gate_slot = _gate_slot(hint, covered and train)
-        out = torch.empty((R, 3), device=dev)
-        if pair or infer_pair:
-            # both heads are done: weights and composite of a ray in one launch (tn_render_rays_fwd, bit-identical to the two)
-            L.call("tn_render_rays_fwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), C.c_float(thr), L.ptr(weights),
-                   L.ptr(out), L.ptr(gate_slot), C.c_int64(n), C.c_int64(R))
-        elif gate_slot is not None:
-            L.call("tn_weights_fwd_gate", dev, L.ptr(sigma), L.ptr(steps), L.ptr(info), C.c_float(thr), L.ptr(weights), L.ptr(gate_slot),
-                   C.c_int64(n), C.c_int64(R))
-        else:
-            L.call("tn_weights_fwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(info), C.c_float(thr), L.ptr(weights),
-                   C.c_int64(n), C.c_int64(R))
-        if pair or infer_pair:
-            pass
-        elif ws_r is not None:
-            L.call("tn_mlp_fwd_stash", dev, C.byref(rdesc), L.ptr(feat), L.ptr(table), C.c_int64(n), L.ptr(rgbs), L.ptr(ws_r), C.c_int64(rb))
-        else:              # inference: the colour head is only evaluated where the weight is not 0 (core.py:246-251), tile-wise
-            rdesc.row_gate = weights.data_ptr()
-            L.call("tn_mlp_fwd", dev, C.byref(rdesc), L.ptr(feat), L.ptr(table), C.c_int64(n), L.ptr(rgbs), C.c_void_p(None))
-            rdesc.row_gate = None
-        if not (pair or infer_pair):
-            L.call("tn_composite_fwd", dev, L.ptr(rgbs), L.ptr(weights), L.ptr(info), L.ptr(bg), L.ptr(out), C.c_void_p(None),
-                   C.c_int64(n), C.c_int64(R))
-        if gather_sigma and INFER_PAIR and stats is not None:
-            _note_live_fraction(stats, weights)
-        # core.py:246-254: when EVERY sample is masked (w == 0 everywhere) the reference renders the background from constants
-        # that carry no graph, i.e. no parameter receives a gradient from the image loss; here the upstream gradient is gated
-        # (a [1] tensor kept outside save_for_backward: with N > 1 the trainer all-reduces it in place right after this forward
-        # (run.Trainer.step_on_batch) -- the single-GPU step on the union of the ranks' rays is only "empty" when every
-        # rank's is -- so the backward below already reads the all-rank value)
-        ctx.gate_in_slot, ctx.stats = gate_slot is not None, stats
-        ctx.gate = gate_slot if gate_slot is not None else (weights.amax().reshape(1) if train else None)
-        if stats is not None:
-            stats["gate"] = ctx.gate
-            stats["pre_gated"] = ctx.gate_in_slot        # the caller MAY hand in a gated gradient (and must then say so)
-            stats["upstream_gated"] = False
-            if stats.get("maps_handout") is not None:   # NerfRenderer.render_maps: the weights this forward composited with
-                stats["maps_handout"]["weights"] = weights
+            L.call("tn_kplanes_fwd", dev, *kp, C.c_int64(n), L.ptr(feat))
+            if p.fwd is _KpFwd.TRAIN_PAIR:      # both heads in one launch: the feature rows are read from HBM once
+                L.call("tn_mlp_fwd_stash_pair", dev, C.byref(rdesc), C.byref(sdesc), L.ptr(feat), L.ptr(table), C.c_int64(n), L.ptr(rgbs),
+                       L.ptr(sigma), L.ptr(ws_r), C.c_int64(rb), L.ptr(ws_s), C.c_int64(sb))
+            else:
+                _head_fwd(dev, sdesc, feat, None, n, sigma, ws_s, sb)
+        colour = None if p.rays_fwd else lambda w: _head_fwd(dev, rdesc, feat, table, n, rgbs, ws_r, rb, w)
+        out, weights = _composite(ctx, a, p.covered, dev, sigma, steps, rgbs, info, bg, colour, rays=p.rays_fwd)
+        if p.note_live:
+            _note_live_fraction(a.stats, weights)
         ctx.save_for_backward(packed, info, bg, freqs, feat, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params)
-        ctx.cfg = (n_freqs, n_planes, n_sigma, accumulate, stride, sb, rb, covered)
-        ctx.lean = lean
-        ctx.arena = arena
-        ctx.param_refs = params if accumulate else None
-        ctx.planes_ready = hint.get("planes_ready") if (hint is not None and accumulate) else None
+        ctx.call, ctx.plan, ctx.planes_ready = a, p, ready
+        ctx.param_refs = params if a.accumulate else None
         return out
 
     @staticmethod
     def backward(ctx: Any, grad_out: torch.Tensor):  # type: ignore
         packed, info, bg, freqs, feat, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params = ctx.saved_tensors
-        n_freqs, n_planes, n_sigma, accumulate, stride, sb, rb, covered = ctx.cfg
-        planes = list(params[:n_planes])
-        sig_p = [p.contiguous() for p in params[n_planes:n_planes + n_sigma]]
-        rgb_p = [p.contiguous() for p in params[n_planes + n_sigma:]]
-        dev = packed.device
-        n, R = packed.size(0), info.size(0)
-        F = feat.size(1)
-        g_out = grad_out.contiguous()
-        if ctx.gate is not None and not _upstream_is_gated(ctx):
-            g_out = g_out * (ctx.gate > 0).to(g_out.dtype)       # "Empty iteration": zero gradients, as on the module-by-module path
-
-        def grad_buffer(p: torch.Tensor, ref: Optional[torch.Tensor]):
-            if accumulate and ref is not None and ref.is_leaf and ref.grad is not None and ref.grad.stride() == p.stride():
-                return ref.grad, True
-            return torch.zeros_like(p), False
-
-        refs: Sequence[Optional[torch.Tensor]] = ctx.param_refs if ctx.param_refs is not None else [None] * len(params)
-        bufs = [grad_buffer(p, r) for p, r in zip(params, refs)]
-        g_planes = [b[0] for b in bufs[:n_planes]]
-        g_sig = [b[0] for b in bufs[n_planes:n_planes + n_sigma]]
-        g_rgb = [b[0] for b in bufs[n_planes + n_sigma:]]
-
-        arena = ctx.arena
-        g_rgbs = _alloc(arena, "g_rgbs", (n, 3), dev)
-        g_sigma = _alloc(arena, "g_sigma", (n,), dev)
-        if not covered:              # samples no ray owns: zero gradient, not whatever the arena held (the kernel writes every
-            g_rgbs.zero_(); g_sigma.zero_()      # sample a ray owns)
-        # composite -> (rgbs, weights) and weights -> sigma as one launch per ray (the weights' gradient needs only the composite's)
-        L.call("tn_render_rays_bwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), L.ptr(weights), L.ptr(g_out),
-               L.ptr(g_rgbs), L.ptr(g_sigma), C.c_int64(n), C.c_int64(R))
-        g_feat = _alloc(arena, "g_feat", (n, F), dev)
-        nr, ns = len(rgb_p) // 2, len(sig_p) // 2
-        gw_r = (C.c_void_p * nr)(*[g.data_ptr() for g in g_rgb[0::2]])
-        gb_r = (C.c_void_p * nr)(*[g.data_ptr() for g in g_rgb[1::2]])
-        gw_s = (C.c_void_p * ns)(*[g.data_ptr() for g in g_sig[0::2]])
-        gb_s = (C.c_void_p * ns)(*[g.data_ptr() for g in g_sig[1::2]])
-        kdesc, keep = _kplanes_desc(planes)
-        gp = ((C.c_void_p * 3) * L.TN_KPLANES_MAX_SCALES)()
-        for s in range(kdesc.n_scales):
-            for p in range(3):
-                gp[s][p] = _hwc(g_planes[3 * s + p]).data_ptr()
-        scattered = False
-
-        def scatter():
-            L.call("tn_kplanes_bwd", dev, C.byref(kdesc), L.ptr(packed), C.c_int64(7), C.c_int64(n), L.ptr(g_feat), gp)
-        if ws_r is not None and ws_s is not None and PAIR_BACKWARD and F % 32 == 0 and ns == 2 and sig_p[0].size(0) == 64 and rgb_p[0].size(0) == 64:
-            # both heads in one data-gradient pass: d/d feat is written once as the sum of the two
-            lean_bit = L.MLP_LEAN if ctx.lean else 0
-            rdesc = _mlp_desc(rgb_p, F, L.ENC_AUX_CAT, n_freqs, L.ACT_SIGMOID, freqs, L.MLP_STASHED | lean_bit, ray_ids, stride)
-            sdesc = _mlp_desc(sig_p, F, L.ENC_NONE, 0, L.ACT_EXP_M1, None, L.MLP_STASHED | lean_bit)
-            base_flags = rdesc.flags                    # (STASHED + the matrix-mode bit + LEAN: the phase bits are OR-ed in, nothing is dropped)
-            pair_args = (C.byref(sdesc), L.ptr(feat), L.ptr(table), L.ptr(g_rgbs), L.ptr(g_sigma),
-                         C.c_int64(n), gw_r, gb_r, gw_s, gb_s, L.ptr(g_feat), L.ptr(ws_r), C.c_int64(rb), L.ptr(ws_s), C.c_int64(sb))
-            scatter_fused = FUSE_SCATTER and kdesc.n_scales == 3 and kdesc.channels == 32 and len(keep) == 9
-            if scatter_fused:
-                # data gradients of both heads AND the plane scatter in one launch: d loss / d features stays in registers
-                def chain_and_weights(flags):
-                    rdesc.flags = base_flags | flags
-                    L.call("tn_kplanes_mlp_bwd_pair", dev, C.byref(kdesc), L.ptr(packed), C.c_int64(7), gp, C.byref(rdesc), C.byref(sdesc),
-                           L.ptr(feat), L.ptr(table), L.ptr(g_rgbs), L.ptr(g_sigma), C.c_int64(n), gw_r, gb_r, gw_s, gb_s, C.c_void_p(None),
-                           L.ptr(ws_r), C.c_int64(rb), L.ptr(ws_s), C.c_int64(sb))
-                # two calls (chain + scatter kernel, then the weight-gradient kernels): the same launches as one call makes, but the
-                # plane gradients are final in between -- with N > 1 their all-reduce starts there and travels under the
-                # weight-gradient kernels -- and each half can be timed on its own (bench.py)
-                chain_and_weights(L.MLP_CHAIN_ONLY)
-                if ctx.planes_ready is not None:
-                    ctx.planes_ready(g_planes)
-                chain_and_weights(L.MLP_WGRAD_ONLY)
-                scattered = True
-            elif ctx.planes_ready is not None:
-                # N > 1: data gradients -> plane scatter -> hand the finished plane gradients to the caller (it starts their
-                # all-reduce) -> weight gradients of the heads, which run while the planes are on the wire
-                rdesc.flags = base_flags | L.MLP_CHAIN_ONLY
-                L.call("tn_mlp_bwd_pair", dev, C.byref(rdesc), *pair_args)
-                scatter()
-                scattered = True
-                ctx.planes_ready(g_planes)
-                rdesc.flags = base_flags | L.MLP_WGRAD_ONLY
-                L.call("tn_mlp_bwd_pair", dev, C.byref(rdesc), *pair_args)
+        a, p = ctx.call, ctx.plan
+        planes, sig_p, rgb_p = a.split(params)
+        dev, n, F = packed.device, packed.size(0), feat.size(1)
+        g_rgbs, g_sigma = _rays_bwd(ctx, grad_out, sigma, steps, rgbs, info, bg, weights)
+        grads, returned = _grad_buffers(ctx, params)
+        g_planes, k = grads[:a.n_planes], a.n_planes + a.n_sigma
+        gw = _grad_ptrs(grads[a.n_planes:k], grads[k:])
+        g_feat = _alloc(a.arena, "g_feat", (n, F), dev)
+        kdesc, _ = _kplanes_desc(planes)
+        gp = ((C.c_void_p * 3) * L.TN_KPLANES_MAX_SCALES)(*[tuple(_hwc(g).data_ptr() for g in g_planes[3 * s:3 * s + 3])
+                                                              for s in range(kdesc.n_scales)])
+        if p.bwd is _KpBwd.SEPARATE:          # g_feat += d sigma / d feat
+            rflags, sflags = L.MLP_STASHED if ws_r is not None else 0, L.MLP_ACCUM_GRAD_X | (L.MLP_STASHED if ws_s is not None else 0)
+        else:                                 # both heads in one data-gradient pass: d / d feat is written once as the sum of the two
+            rflags = sflags = L.MLP_STASHED | p.flags
+        rdesc, sdesc = _head_descs(sig_p, rgb_p, F, a.n_freqs, freqs, ray_ids, table, rflags, sflags)
+        rb, sb = p.rb, p.sb
+        if ws_r is None:                      # (a head whose forward had no workspace: SEPARATE only)
+            ws_r, rb = _workspace(rdesc, n, dev, a.arena, "ws_rgb")
+        if ws_s is None:
+            ws_s, sb = _workspace(sdesc, n, dev, a.arena, "ws_sigma")
+        base_flags = rdesc.flags              # (STASHED + the matrix-mode bit + LEAN: the phase bits are OR-ed in, nothing is dropped)
+        # SCATTER_CHAIN and PAIR_SPLIT: two calls, data gradients (+ plane scatter) then weight gradients -- the same launches as one
+        # call makes, but the plane gradients are final in between: with N > 1 their all-reduce starts there and travels under the
+        # weight-gradient kernels, and each half can be timed on its own (bench.py)
+        for phase in (0,) if p.bwd in (_KpBwd.SEPARATE, _KpBwd.PAIR) else (L.MLP_CHAIN_ONLY, L.MLP_WGRAD_ONLY):
+            rdesc.flags = base_flags | phase
+            if p.bwd is _KpBwd.SCATTER_CHAIN:       # d loss / d features stays in registers
+                L.call("tn_kplanes_mlp_bwd_pair", dev, C.byref(kdesc), L.ptr(packed), C.c_int64(7), gp, C.byref(rdesc), C.byref(sdesc),
+                       L.ptr(feat), L.ptr(table), L.ptr(g_rgbs), L.ptr(g_sigma), C.c_int64(n), *gw, C.c_void_p(None), L.ptr(ws_r),
+                       C.c_int64(rb), L.ptr(ws_s), C.c_int64(sb))
             else:
-                L.call("tn_mlp_bwd_pair", dev, C.byref(rdesc), *pair_args)
-        else:
-            if ctx.lean:
-                raise RuntimeError("tinynerf_amd: the forward ran with TN_MLP_LEAN (no hidden activations in the workspace) but this backward "
-                                   "is not the paired form that rebuilds them")
-            stashed = L.MLP_STASHED if ws_r is not None else 0
-            rdesc = _mlp_desc(rgb_p, F, L.ENC_AUX_CAT, n_freqs, L.ACT_SIGMOID, freqs, stashed, ray_ids, stride)
-            if ws_r is None:
-                ws_r, rb = _workspace(rdesc, n, dev, arena, "ws_rgb")
-            L.call("tn_mlp_bwd", dev, C.byref(rdesc), L.ptr(feat), L.ptr(table), L.ptr(g_rgbs), C.c_int64(n), gw_r, gb_r, L.ptr(g_feat),
-                   L.ptr(ws_r), C.c_int64(rb))
-            stashed = L.MLP_STASHED if ws_s is not None else 0
-            sdesc = _mlp_desc(sig_p, F, L.ENC_NONE, 0, L.ACT_EXP_M1, None, L.MLP_ACCUM_GRAD_X | stashed)   # g_feat += d sigma / d feat
-            if ws_s is None:
-                ws_s, sb = _workspace(sdesc, n, dev, arena, "ws_sigma")
-            L.call("tn_mlp_bwd", dev, C.byref(sdesc), L.ptr(feat), C.c_void_p(None), L.ptr(g_sigma), C.c_int64(n), gw_s, gb_s,
-                   L.ptr(g_feat), L.ptr(ws_s), C.c_int64(sb))
-        if not scattered:      # plane scatter
-            scatter()
-        grads = [None if in_place else g for (g, in_place) in bufs]
-        return (None, None, None, None, None, None, None, None, None, None, None, None, None, *grads)
+                _heads_bwd(dev, p.bwd is not _KpBwd.SEPARATE, rdesc, sdesc, feat, table, g_rgbs, g_sigma, gw, g_feat, ws_r, rb, ws_s, sb)
+                if phase != L.MLP_WGRAD_ONLY:
+                    L.call("tn_kplanes_bwd", dev, C.byref(kdesc), L.ptr(packed), C.c_int64(7), C.c_int64(n), L.ptr(g_feat), gp)
+            if phase == L.MLP_CHAIN_ONLY and ctx.planes_ready is not None:
+                ctx.planes_ready(g_planes)
+        return (None, None, None, None, None, *returned)
 
 
 class _MergeLast(Function):
@@ -425,158 +509,75 @@ class _RenderHeads(Function):
     the composite in both directions, as in the reference (core.py:243-249)."""
 
     @staticmethod
-    def forward(ctx: Any, feat: torch.Tensor, packed: torch.Tensor, info: torch.Tensor, bg: Optional[torch.Tensor], thr: float,
-                freqs: torch.Tensor, n_freqs: int, n_sigma: int, accumulate: bool, arena: Optional[Arena], train: bool,
-                hint: Optional[dict], stats: Optional[dict], link: Optional[dict], *params: torch.Tensor) -> torch.Tensor:  # type: ignore
-        sig_p = [p.contiguous() for p in params[:n_sigma]]
-        rgb_p = [p.contiguous() for p in params[n_sigma:]]
+    def forward(ctx: Any, a: _Call, feat: torch.Tensor, packed: torch.Tensor, info: torch.Tensor, bg: Optional[torch.Tensor],
+                freqs: torch.Tensor, *params: torch.Tensor) -> torch.Tensor:  # type: ignore
+        _, sig_p, rgb_p = a.split(params)
         feat = feat.contiguous()
-        # `link`: row views of the wide stack that produced `feat` (models._FusedMLP.forward, harness only): feat^T as
+        # `a.link`: row views of the wide stack that produced `feat` (models._FusedMLP.forward, harness only): feat^T as
         # [feature][32-sample] rows in that stack's workspace and the slot where it takes d loss / d feat in the same layout
-        offered = link
-        if not (link and train and link.get("n") == feat.size(0) and link.get("y_ptr") == feat.data_ptr() and link.get("width") == feat.size(1)
-                and feat.size(1) in (128, 256)):
-            link = None
-        if link is None and offered and offered.get("rows_only"):
+        link = a.link if (a.link and a.train and a.link.get("n") == feat.size(0) and a.link.get("y_ptr") == feat.data_ptr()
+                          and a.link.get("width") == feat.size(1) and feat.size(1) in (128, 256)) else None
+        if link is None and a.link and a.link.get("rows_only"):
             raise RuntimeError("tinynerf_amd: the feature stack left its output as workspace rows only (TN_MLP_ROWS_ONLY) but this render "
                                "node cannot read them")
-        ctx.link = link
         dev = L.require_cuda(feat, packed, info, *sig_p, *rgb_p)
-        n, R = packed.size(0), info.size(0)
-        F = feat.size(1)
-        sdesc = _mlp_desc(sig_p, F, L.ENC_NONE, 0, L.ACT_EXP_M1, None)
+        n, R, F = packed.size(0), info.size(0), feat.size(1)
+        covered = _covered(a.hint, packed, R)
         if link is not None:
             # cat[PE(d), d] (models.py:87) once per RAY as a table the kernels index through the ray id of every sample
             # (TN_ENC_AUX_CAT, as in the K-Planes node): the colour head then takes the plain-column first layer.  Its weight
             # gradient over a 256-wide x needs the row-operand kernel, hence only with row views
-            table, ray_ids, stride, steps = _ray_aux(packed, info, freqs, n_freqs, arena, hint)
-            rdesc = _mlp_desc(rgb_p, F, L.ENC_AUX_CAT, n_freqs, L.ACT_SIGMOID, freqs, 0, ray_ids, stride)
+            table, ray_ids, steps = _ray_aux(packed, info, freqs, a.n_freqs, a.arena, a.hint)
         else:
-            # cat[PE(d), d] is evaluated per sample inside the colour head's kernels (TN_ENC_DIR_CAT)
-            if hint is not None and hint.get("key") == (packed.data_ptr(), n, R):
-                steps = hint["steps"]
-            else:
-                steps = _alloc(arena, "steps", (n,), dev)
-                steps.copy_(packed[:, 6])
-            table = _alloc(arena, "dirs", (n, 3), dev)
-            table.copy_(packed[:, 3:6])
-            ray_ids, stride = None, 0
-            rdesc = _mlp_desc(rgb_p, F, L.ENC_DIR_CAT, n_freqs, L.ACT_SIGMOID, freqs)
-        ws_s = ws_r = None
-        sb = rb = 0
-        # f16x2 heads read their first-layer operands from the stack's row view (128-byte rows instead of 16 bytes per lane and
-        # sample); once a forward has done so the stack stops writing the row-major feat (TN_MLP_ROWS_ONLY / TN_MLP_X_FROM_ROWS)
-        rows_fwd = link is not None and MATMUL_F16X2()
-        if train:
-            ws_s, sb = _workspace(sdesc, n, dev, arena, "ws_sigma")
-            ws_r, rb = _workspace(rdesc, n, dev, arena, "ws_rgb")
-            if ws_s is None or ws_r is None:
-                raise RuntimeError("tinynerf_amd: these decoder shapes are outside the fused render node (use renderer.fused = False)")
-        sigma = _alloc(arena, "sigma", (n,), dev)
-        rgbs = _alloc(arena, "rgbs", (n, 3), dev)
-        if rows_fwd:
+            steps = a.hint["steps"] if covered else _alloc(a.arena, "steps", (n,), dev).copy_(packed[:, 6])
+            table = _alloc(a.arena, "dirs", (n, 3), dev).copy_(packed[:, 3:6])
+            ray_ids = None
+        rdesc, sdesc = _head_descs(sig_p, rgb_p, F, a.n_freqs, freqs, ray_ids, table)
+        ws_s, sb = _workspace(sdesc, n, dev, a.arena, "ws_sigma") if a.train else (None, 0)
+        ws_r, rb = _workspace(rdesc, n, dev, a.arena, "ws_rgb") if a.train else (None, 0)
+        p = _plan_heads(F, sig_p, rgb_p, a.train, link, sb, rb, covered)
+        sigma = _alloc(a.arena, "sigma", (n,), dev)
+        rgbs = _alloc(a.arena, "rgbs", (n, 3), dev)
+        if p.rows_fwd:
             for d in (rdesc, sdesc):
                 d.x_rows, d.x_rows_tile_stride = link["y_rows"], link["stride"]
-                if link.get("rows_only"):
-                    d.flags |= L.MLP_X_FROM_ROWS
-        if train:
-            L.call("tn_mlp_fwd_stash", dev, C.byref(sdesc), L.ptr(feat), C.c_void_p(None), C.c_int64(n), L.ptr(sigma), L.ptr(ws_s), C.c_int64(sb))
-        else:
-            L.call("tn_mlp_fwd", dev, C.byref(sdesc), L.ptr(feat), C.c_void_p(None), C.c_int64(n), L.ptr(sigma), C.c_void_p(None))
-        weights = _alloc(arena, "weights", (n,), dev)
-        covered = hint is not None and hint.get("key") == (packed.data_ptr(), n, R)
-        if not covered:
-            weights.zero_()          # cuda.cu:84 (zeros_like): samples outside every (start, count) keep weight 0
-        gate_slot = _gate_slot(hint, covered and train)       # (see _RenderKPlanes)
-        out = torch.empty((R, 3), device=dev)
-        if train:          # the colour head runs on every sample: weights and composite of a ray behind it, in one launch
-            L.call("tn_mlp_fwd_stash", dev, C.byref(rdesc), L.ptr(feat), L.ptr(table), C.c_int64(n), L.ptr(rgbs), L.ptr(ws_r), C.c_int64(rb))
-            L.call("tn_render_rays_fwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), C.c_float(thr), L.ptr(weights),
-                   L.ptr(out), L.ptr(gate_slot), C.c_int64(n), C.c_int64(R))
-        else:              # inference: the colour head is only evaluated where the weight is not 0 (core.py:246-251), tile-wise
-            L.call("tn_weights_fwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(info), C.c_float(thr), L.ptr(weights), C.c_int64(n), C.c_int64(R))
-            rdesc.row_gate = weights.data_ptr()
-            L.call("tn_mlp_fwd", dev, C.byref(rdesc), L.ptr(feat), L.ptr(table), C.c_int64(n), L.ptr(rgbs), C.c_void_p(None))
-            rdesc.row_gate = None
-            L.call("tn_composite_fwd", dev, L.ptr(rgbs), L.ptr(weights), L.ptr(info), L.ptr(bg), L.ptr(out), C.c_void_p(None),
-                   C.c_int64(n), C.c_int64(R))
-        ctx.gate_in_slot, ctx.stats = gate_slot is not None, stats
-        ctx.gate = gate_slot if gate_slot is not None else (weights.amax().reshape(1) if train else None)   # "Empty iteration", see _RenderKPlanes
-        if stats is not None:
-            stats["gate"] = ctx.gate
-            stats["pre_gated"] = ctx.gate_in_slot
-            stats["upstream_gated"] = False
-            if stats.get("maps_handout") is not None:   # (see _RenderKPlanes)
-                stats["maps_handout"]["weights"] = weights
+                d.flags |= L.MLP_X_FROM_ROWS if p.x_from_rows else 0
+        _head_fwd(dev, sdesc, feat, None, n, sigma, ws_s, sb)
+        # training: the colour head runs on every sample, weights and composite of a ray behind it in one launch
+        out, weights = _composite(ctx, a, covered, dev, sigma, steps, rgbs, info, bg,
+                                  lambda w: _head_fwd(dev, rdesc, feat, table, n, rgbs, ws_r, rb, w), rays=a.train)
         ctx.save_for_backward(feat, info, bg, freqs, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params)
-        ctx.cfg = (n_freqs, n_sigma, accumulate, stride, sb, rb, covered)
-        ctx.arena = arena
-        ctx.param_refs = params if accumulate else None
+        ctx.call, ctx.plan, ctx.link = a, p, link
+        ctx.param_refs = params if a.accumulate else None
         return out
 
     @staticmethod
     def backward(ctx: Any, grad_out: torch.Tensor):  # type: ignore
         feat, info, bg, freqs, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params = ctx.saved_tensors
-        n_freqs, n_sigma, accumulate, stride, sb, rb, covered = ctx.cfg
-        sig_p = [p.contiguous() for p in params[:n_sigma]]
-        rgb_p = [p.contiguous() for p in params[n_sigma:]]
-        dev = feat.device
-        n, R, F = feat.size(0), info.size(0), feat.size(1)
-        g_out = grad_out.contiguous()
-        if ctx.gate is not None and not _upstream_is_gated(ctx):
-            g_out = g_out * (ctx.gate > 0).to(g_out.dtype)
-        refs: Sequence[Optional[torch.Tensor]] = ctx.param_refs if ctx.param_refs is not None else [None] * len(params)
-
-        def grad_buffer(p: torch.Tensor, ref: Optional[torch.Tensor]):
-            if accumulate and ref is not None and ref.is_leaf and ref.grad is not None and ref.grad.stride() == p.stride():
-                return ref.grad, True
-            return torch.zeros_like(p), False
-        bufs = [grad_buffer(p, r) for p, r in zip(params, refs)]
-        g_sig = [b[0] for b in bufs[:n_sigma]]
-        g_rgb = [b[0] for b in bufs[n_sigma:]]
-        arena = ctx.arena
-        g_rgbs = _alloc(arena, "g_rgbs", (n, 3), dev)
-        g_sigma = _alloc(arena, "g_sigma", (n,), dev)
-        if not covered:              # (the kernel writes every sample a ray owns)
-            g_rgbs.zero_(); g_sigma.zero_()
-        L.call("tn_render_rays_bwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), L.ptr(weights), L.ptr(g_out),
-               L.ptr(g_rgbs), L.ptr(g_sigma), C.c_int64(n), C.c_int64(R))
-        link = ctx.link
+        a, p, link = ctx.call, ctx.plan, ctx.link
+        _, sig_p, rgb_p = a.split(params)
+        dev, (n, F) = feat.device, feat.shape
+        g_rgbs, g_sigma = _rays_bwd(ctx, grad_out, sigma, steps, rgbs, info, bg, weights)
+        grads, returned = _grad_buffers(ctx, params)
+        gw = _grad_ptrs(grads[:a.n_sigma], grads[a.n_sigma:])
         # with row views the heads write d loss / d feat straight into the feature stack's workspace (rows) and read feat^T from
         # there for their first layers' weight gradients; autograd gets a placeholder of the right shape (no memory behind it)
         g_feat = _empty_rows(n, F, dev) if link is None else None      # handed to autograd (the field's backward): not an arena view
-        nr, ns = len(rgb_p) // 2, len(sig_p) // 2
-        gw_r = (C.c_void_p * nr)(*[g.data_ptr() for g in g_rgb[0::2]])
-        gb_r = (C.c_void_p * nr)(*[g.data_ptr() for g in g_rgb[1::2]])
-        gw_s = (C.c_void_p * ns)(*[g.data_ptr() for g in g_sig[0::2]])
-        gb_s = (C.c_void_p * ns)(*[g.data_ptr() for g in g_sig[1::2]])
-        if link is not None:
-            rdesc = _mlp_desc(rgb_p, F, L.ENC_AUX_CAT, n_freqs, L.ACT_SIGMOID, freqs, L.MLP_STASHED, ray_ids, stride)
-        else:
-            rdesc = _mlp_desc(rgb_p, F, L.ENC_DIR_CAT, n_freqs, L.ACT_SIGMOID, freqs, L.MLP_STASHED)
-        sdesc = _mlp_desc(sig_p, F, L.ENC_NONE, 0, L.ACT_EXP_M1, None, L.MLP_ACCUM_GRAD_X | L.MLP_STASHED)     # g_feat += d sigma / d feat
+        rdesc, sdesc = _head_descs(sig_p, rgb_p, F, a.n_freqs, freqs, ray_ids, table, L.MLP_STASHED,
+                                   L.MLP_STASHED | (0 if p.pair_bwd else L.MLP_ACCUM_GRAD_X))      # unpaired: g_feat += d sigma / d feat
         if link is not None:
             for d in (rdesc, sdesc):
                 d.x_rows, d.grad_x_rows = link["y_rows"], link["grad_rows"]
                 d.x_rows_tile_stride = d.grad_x_rows_tile_stride = link["stride"]
                 if link.get("skipped_last"):     # x is the producer's last HIDDEN activation: d / d (its pre-activation) = relu' * ...
                     d.grad_x_mask_rows, d.grad_x_mask_tile_stride = link["mask_rows"], link["stride"]
-        if link is not None and HEADS_PAIR_BACKWARD and F % 64 == 0 and ns == 2 and nr == 5 and sig_p[0].size(0) == 64 and rgb_p[0].size(0) == 64:
-            # one call for both heads: their first layers' x-column weight gradients share a launch (and the x rows), and behind the
-            # 128-wide stack d loss / d feat is written once as the sum of the two data gradients (mlp_bwd2.hip, bwd_pair_common)
-            sdesc.flags &= ~L.MLP_ACCUM_GRAD_X
-            L.call("tn_mlp_bwd_pair", dev, C.byref(rdesc), C.byref(sdesc), L.ptr(feat), L.ptr(table), L.ptr(g_rgbs), L.ptr(g_sigma),
-                   C.c_int64(n), gw_r, gb_r, gw_s, gb_s, L.ptr(g_feat), L.ptr(ws_r), C.c_int64(rb), L.ptr(ws_s), C.c_int64(sb))
-        else:
-            L.call("tn_mlp_bwd", dev, C.byref(rdesc), L.ptr(feat), L.ptr(table), L.ptr(g_rgbs), C.c_int64(n), gw_r, gb_r, L.ptr(g_feat),
-                   L.ptr(ws_r), C.c_int64(rb))
-            L.call("tn_mlp_bwd", dev, C.byref(sdesc), L.ptr(feat), C.c_void_p(None), L.ptr(g_sigma), C.c_int64(n), gw_s, gb_s, L.ptr(g_feat),
-                   L.ptr(ws_s), C.c_int64(sb))
+        # pair: both heads' first layers' x-column weight gradients share a launch (and the x rows), and behind the 128-wide stack
+        # d loss / d feat is written once as the sum of the two data gradients (mlp_bwd2.hip, bwd_pair_common)
+        _heads_bwd(dev, p.pair_bwd, rdesc, sdesc, feat, table, g_rgbs, g_sigma, gw, g_feat, ws_r, p.rb, ws_s, p.sb)
         if link is not None:
             link["delivered"] = True
             g_feat = torch.empty(1, device=dev).expand(n, F)
-        grads = [None if in_place else g for (g, in_place) in bufs]
-        return (g_feat, None, None, None, None, None, None, None, None, None, None, None, None, None, *grads)
+        return (None, g_feat, None, None, None, None, *returned)
 
 
 def _mergeable(producer, sig_p, rgb_p) -> bool:
@@ -590,9 +591,6 @@ def _mergeable(producer, sig_p, rgb_p) -> bool:
     # ... and the kernel side can actually stop this stack at its last hidden activation (slab-eligible f16x2 stack: positional encoding with
     # <= 64 slots or <= 64 plain inputs, out == H): asked of the library itself (host-only, no launch) with the descriptor of the
     # stack's previous forward -- shapes alone would arm TN_MLP_SKIP_LAST for stacks that then fail with TN_E_CONFIG mid-step
-    import ctypes as C
-    from . import _lib as L
-    from .models import _mlp_desc
     sc = producer.__dict__.get("scratch")
     cfg = sc[4].get("last_cfg") if sc is not None and len(sc) > 4 else None
     if cfg is None:
@@ -635,8 +633,8 @@ def render(renderer, packed: torch.Tensor, info: torch.Tensor, thr: float, accum
     if isinstance(fm, KPlanesFeatureField):
         planes = fm.plane_tensors()
         train = torch.is_grad_enabled() and any(p.requires_grad for p in (*planes, *sig_p, *rgb_p))
-        return _RenderKPlanes.apply(packed.contiguous(), info.contiguous(), bg, float(thr), cd.pe.freqs, cd.n_freqs, len(planes),
-                                    len(sig_p), accumulate_into_grad, arena, train, hint, stats, *planes, *sig_p, *rgb_p)
+        a = _Call(float(thr), cd.n_freqs, len(planes), len(sig_p), accumulate_into_grad, arena, train, hint, stats)
+        return _RenderKPlanes.apply(a, packed.contiguous(), info.contiguous(), bg, cd.pe.freqs, *planes, *sig_p, *rgb_p)
     # harness: the stack whose row view this node matched last time may leave its output as rows only (TN_MLP_ROWS_ONLY) -- armed for
     # exactly this forward; _RenderHeads fails loudly if it then cannot read the rows
     producer = renderer.__dict__.get("_rows_producer")
@@ -675,5 +673,5 @@ def render(renderer, packed: torch.Tensor, info: torch.Tensor, thr: float, accum
         wc, bc, ws_, bs_ = _MergeLast.apply(accumulate_into_grad, pe, rgb_p[0], rgb_p[1], sig_p[0], sig_p[1], w_last, b_last)
         rgb_p = [wc, bc, *rgb_p[2:]]
         sig_p = [ws_, bs_, *sig_p[2:]]
-    return _RenderHeads.apply(feat, packed.contiguous(), info.contiguous(), bg, float(thr), cd.pe.freqs, cd.n_freqs, len(sig_p),
-                              accumulate_into_grad, arena, train, hint, stats, link, *sig_p, *rgb_p)
+    a = _Call(float(thr), cd.n_freqs, 0, len(sig_p), accumulate_into_grad, arena, train, hint, stats, link)
+    return _RenderHeads.apply(a, feat, packed.contiguous(), info.contiguous(), bg, cd.pe.freqs, *sig_p, *rgb_p)
