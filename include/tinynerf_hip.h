@@ -531,6 +531,36 @@ int tn_render_rays_bwd(const float *sigmas, const float *steps, const float *rgb
  * image loss then reaches no parameter); sumsq as in tn_mse_grad. */
 int tn_mse_grad_gated(const float *rendered, const float *target, int64_t n, float scale, const float *scale_dev,
                       const float *gate, float *grad, double *sumsq, void *stream);
+
+/* Distortion loss of Mip-NeRF 360 on packed rays.  For ray r with samples k = 0..count-1, weights w_k (tn_weights_fwd /
+ * tn_render_rays_fwd: what the forward composited with), normalised positions m_k and widths d_k:
+ *   L_r       = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
+ *   dL_r/dw_i = 2 sum_j w_j |m_i - m_j| + (2/3) w_i d_i                  (for every sample, also where w_i == 0)
+ * m, d follow from t_values (tn_sample_pack_t: the sample's ray parameter, increasing along a ray) and steps through `warp`,
+ * x = (t - near) / range:
+ *   TN_DIST_LINEAR     m = x,    d = step / range                        (AABB marcher: near 0, range = the box diagonal)
+ *   TN_DIST_UNBOUNDED  m = g(x), d = g'(x) step / range, g(x) = x / 2 for x < 1, 1 - 1 / (2 x) otherwise -- the inverse of the
+ *                      unbounded marcher's table (core.py:52), near = its near, range = its uniform_range: m is the marcher's
+ *                      uniform parameter in [0, 1).
+ * Evaluated in O(count) per ray from fp32 prefix sums with m taken relative to the ray's first sample (the loss is shift
+ * invariant; unshifted prefixes cancel).  One wave per ray; info must be 8-byte aligned; no gradient flows to t or step.
+ * TN_E_CONFIG for an unknown warp or range <= 0.  No reference call site: the reference has no regulariser on the weights
+ * (its only one is the planes' total variation, run.py:254-256). */
+enum { TN_DIST_LINEAR = 0, TN_DIST_UNBOUNDED = 1 };
+/* loss[r] = L_r (0 for rays without samples); sum (may be NULL; one fp64 device scalar, caller zeroes) += sum_r loss[r] */
+int tn_distortion_fwd(const float *weights, const float *t_values, const float *steps, const int32_t *info, int64_t n_rays,
+                      int32_t warp, float near, float range, float *loss, double *sum, void *stream);
+/* grad_weights[i] = c * (grad_loss ? grad_loss[r] : 1) * dL_r/dw_i for every sample a ray owns,
+ * c = scale * (scale_dev ? scale_dev[0] : 1) -- the convention of tn_mse_grad */
+int tn_distortion_bwd(const float *weights, const float *t_values, const float *steps, const int32_t *info, int64_t n_rays,
+                      int32_t warp, float near, float range, const float *grad_loss, float scale, const float *scale_dev,
+                      float *grad_weights, void *stream);
+/* tn_render_rays_bwd with grad_weights_extra[i] ([n_samples], e.g. tn_distortion_bwd's output) added to sample i's composite
+ * gradient -- (d - gbg) + extra, in that order -- before the weights backward (cuda.cu:49-56, no termination: the extra term
+ * also acts on samples with w == 0).  With extra == 0 the outputs are tn_render_rays_bwd's bit for bit. */
+int tn_render_rays_bwd_dw(const float *sigmas, const float *steps, const float *rgbs, const int32_t *info, const float *bg,
+                          const float *weights, const float *grad_rendered, const float *grad_weights_extra, float *grad_rgbs,
+                          float *grad_sigmas, int64_t n_samples, int64_t n_rays, void *stream);
 /* The harness' batch draw (run.py:225-229, the DataLoader's index_select): rows idx[i] of the [N, 3] ray tables -> out_* [n, 3]
  * in one launch; rgbs / out_rgb may be NULL. */
 int tn_gather_rays(const float *rays_o, const float *rays_d, const float *rgbs, const int32_t *idx, int64_t n,

@@ -21,6 +21,7 @@ MARCH_AABB, MARCH_UNBOUNDED = 0, 1
 CONTRACT_AABB, CONTRACT_MIP360_INF, CONTRACT_MIP360_L2 = 0, 1, 2
 ACT_NONE, ACT_EXP_M1, ACT_SIGMOID, ACT_EXP = 0, 1, 2, 3
 ENC_NONE, ENC_POSENC, ENC_DIR_CAT, ENC_AUX_CAT = 0, 1, 2, 3
+DIST_LINEAR, DIST_UNBOUNDED = 0, 1          # tn_distortion_fwd / tn_distortion_bwd: the warp of t (TN_DIST_*)
 
 
 class SamplerDesc(C.Structure):

@@ -410,6 +410,58 @@ class _Composite(torch.autograd.Function):
         return g_rgb, g_w, None, None
 
 
+def distortion_warp(ray_marcher: RayMarcher) -> Tuple[int, float, float]:
+    """``(warp, near, range)`` of ``RayDistortion`` / ``NerfRenderer.distortion_warp`` for a marcher: the AABB marcher's samples are
+    uniform in t, normalised by the box diagonal (= n_samples * step_size, so a ray spans at most 1); the unbounded marcher's are
+    uniform in u = g((t - near) / uniform_range), the inverse of its table (core.py:52), and the loss is taken in u."""
+    if isinstance(ray_marcher, RayMarcherUnbounded):
+        return L.DIST_UNBOUNDED, float(ray_marcher.near), float(ray_marcher.uniform_range)
+    if isinstance(ray_marcher, RayMarcherAABB):
+        return L.DIST_LINEAR, 0.0, float(_host_floats(ray_marcher.step_size)[0]) * ray_marcher.n_samples
+    raise TypeError(f"no distortion warp for {type(ray_marcher).__name__}")
+
+
+def _check_warp(warp: int, range_: float) -> None:
+    if warp not in (L.DIST_LINEAR, L.DIST_UNBOUNDED) or not range_ > 0:
+        raise ValueError("distortion warp must be (DIST_LINEAR | DIST_UNBOUNDED, near, range > 0)")
+
+
+class RayDistortion(torch.autograd.Function):
+    """Per-ray distortion loss of Mip-NeRF 360, ``L_r = sum_ij w_i w_j |m_i - m_j| + 1/3 sum_i w_i^2 d_i`` (``tn_distortion_fwd``):
+    ``weights, t, steps [N]``, ``info [R,2]`` -> ``[R]``.  ``t`` is the ray parameter of every packed sample
+    (``RayProvider(..., return_t=True)``), ``(warp, near, range)`` come from ``distortion_warp(marcher)``.  Differentiable in
+    ``weights`` only: ``t`` and ``steps`` are sampler outputs."""
+
+    @staticmethod
+    def forward(ctx: Any, weights: torch.Tensor, t: torch.Tensor, steps: torch.Tensor, info: torch.Tensor, warp: int, near: float,
+                range_: float) -> torch.Tensor:  # type: ignore
+        weights, t, steps, info = _f32c(weights), _f32c(t), _f32c(steps), info.contiguous()
+        _check_info(info)
+        _check_warp(warp, range_)
+        if not (weights.dim() == t.dim() == steps.dim() == 1 and weights.size(0) == t.size(0) == steps.size(0)):
+            raise RuntimeError("weights, t and steps must be 1-D and hold one value per packed sample")
+        dev = L.require_cuda(weights, t, steps, info)
+        R = info.size(0)
+        loss = torch.zeros(R, device=dev)
+        if weights.numel() > 0:
+            L.call("tn_distortion_fwd", dev, L.ptr(weights), L.ptr(t), L.ptr(steps), L.ptr(info), C.c_int64(R), C.c_int32(warp),
+                   C.c_float(near), C.c_float(range_), L.ptr(loss), C.c_void_p(None))
+        ctx.save_for_backward(weights, t, steps, info)
+        ctx.warp = (warp, near, range_)
+        return loss
+
+    @staticmethod
+    def backward(ctx: Any, grad_loss: torch.Tensor):  # type: ignore
+        weights, t, steps, info = ctx.saved_tensors
+        warp, near, range_ = ctx.warp
+        grad_loss = _f32c(grad_loss)
+        g_w = torch.zeros_like(weights)          # samples no ray owns keep gradient 0
+        if weights.numel() > 0:
+            L.call("tn_distortion_bwd", weights.device, L.ptr(weights), L.ptr(t), L.ptr(steps), L.ptr(info), C.c_int64(info.size(0)),
+                   C.c_int32(warp), C.c_float(near), C.c_float(range_), L.ptr(grad_loss), C.c_float(1.0), C.c_void_p(None), L.ptr(g_w))
+        return g_w, None, None, None, None, None, None
+
+
 class NerfRenderer(torch.nn.Module):
     def __init__(
         self,
@@ -428,6 +480,8 @@ class NerfRenderer(torch.nn.Module):
         self.fused = True
         self.accumulate_into_grad = False      # harness option: add parameter grads straight into param.grad
         self.reuse_buffers = False             # harness option: capacity-based scratch arena (fused.Arena)
+        # render_with_distortion: (warp, near, range) of the marcher that made the samples (distortion_warp(marcher)); the trainer sets it
+        self.distortion_warp: Optional[Tuple[int, float, float]] = None
         assert hasattr(self.feature_module, "feature_dim"), "feature module requires a feature_dim attribute"
 
     def _bg(self, device: torch.device) -> Optional[torch.Tensor]:
@@ -446,6 +500,10 @@ class NerfRenderer(torch.nn.Module):
         """Module-by-module renderer of core.py:225-267: features -> sigma -> weights -> colour of
         the samples with w > 0 -> per-ray composite.  Each stage is a HIP launch; the fully fused
         K-Planes path lives in ``tinynerf_amd.fused``."""
+        return self._render(packed_samples, packing_info, early_termination_threshold, None)
+
+    def _render(self, packed_samples: torch.Tensor, packing_info: torch.Tensor, early_termination_threshold: float, dist: Optional[dict]):
+        """``forward``; with ``dist`` (render_with_distortion: t and the warp) -> (rgb, per-ray distortion of the weights it composited with)"""
         device = packed_samples.device
         n_samples = packed_samples.size(0)
         n_rays = packing_info.size(0)
@@ -454,7 +512,7 @@ class NerfRenderer(torch.nn.Module):
         if self.fused and n_samples > 0 and n_rays > 0:
             from . import fused
             if fused.supports(self):
-                return fused.render(self, packed_samples, packing_info, early_termination_threshold, self.accumulate_into_grad)
+                return fused.render(self, packed_samples, packing_info, early_termination_threshold, self.accumulate_into_grad, dist)
         empty = n_samples == 0
         if not empty:
             feats = self.feature_module(packed_samples[:, :3])
@@ -479,8 +537,33 @@ class NerfRenderer(torch.nn.Module):
         if handout is not None:             # render_maps: the weights this forward composites with
             handout["weights"] = weights
         if n_rays == 0:
-            return torch.zeros((0, 3), device=device)
-        return _Composite.apply(rgbs, weights, packing_info.contiguous(), bg)
+            rendered = torch.zeros((0, 3), device=device)
+        else:
+            rendered = _Composite.apply(rgbs, weights, packing_info.contiguous(), bg)
+        if dist is None:
+            return rendered
+        if n_rays == 0 or n_samples == 0:
+            return rendered, torch.zeros(n_rays, device=device)
+        return rendered, RayDistortion.apply(weights, dist["t"], packed_samples[:, 6], packing_info, *dist["warp"])
+
+    def render_with_distortion(
+        self,
+        packed_samples: torch.Tensor,  # [n_samples, 7]
+        packing_info: torch.Tensor,  # [n_rays, 2]
+        t: torch.Tensor,  # [n_samples], RayProvider(..., return_t=True)
+        early_termination_threshold: float = 1e-4,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``forward``'s colour (the same bits) and the per-ray distortion loss ``[R]`` of the weights it composited with
+        (``RayDistortion``), both differentiable.  Same dispatch as ``forward``: on the module-by-module path the loss hangs on the
+        weights ``NerfWeights`` returned; the fused nodes hand it out as a second output whose gradient joins the composite's in
+        front of the weights backward (``tn_distortion_bwd`` -> ``tn_render_rays_bwd_dw``).  The warp is ``self.distortion_warp``
+        (``distortion_warp(marcher)``; ``(DIST_LINEAR, 0, 1)`` when unset: t as it is)."""
+        if t.dim() != 1 or t.size(0) != packed_samples.size(0):
+            raise RuntimeError("t must hold one value per packed sample (RayProvider(..., return_t=True))")
+        warp, near, range_ = self.distortion_warp if self.distortion_warp is not None else (L.DIST_LINEAR, 0.0, 1.0)
+        _check_warp(warp, range_)
+        return self._render(packed_samples, packing_info, early_termination_threshold,
+                            {"t": _f32c(t), "warp": (int(warp), float(near), float(range_))})
 
     @torch.no_grad()
     def _maps(self, weights: torch.Tensor, packing_info: torch.Tensor, t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

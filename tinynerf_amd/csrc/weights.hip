@@ -99,12 +99,13 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void weights_fwd_kernel(
 // between the reduction (pass 1 of cuda.cu:51) and the prefix sweep (pass 2, cuda.cu:52-56).
 // COMP: d loss / d weights is not read but formed here from the composite's upstream gradient (composite_bwd_kernel below: <rgb, g>
 // - <bg, g>, and grad_rgbs = w g written on the way) -- the same arithmetic, one launch and no grad_weights round trip.
-template <int MAXC, bool COMP>
+// EXTRA (with COMP): a second gradient of the weights -- the distortion loss', distortion_bwd_kernel below -- is added to the composite's.
+template <int MAXC, bool COMP, bool EXTRA = false>
 __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void weights_bwd_kernel(
     const float *__restrict__ sigmas, const float *__restrict__ steps, const int32_t *__restrict__ info,
     const float *__restrict__ weights, const float *__restrict__ grad_w, float *__restrict__ grad_sigmas,
     int64_t n_rays, const float *__restrict__ rgbs = nullptr, const float *__restrict__ bg = nullptr,
-    const float *__restrict__ grad_rendered = nullptr, float *__restrict__ grad_rgbs = nullptr)
+    const float *__restrict__ grad_rendered = nullptr, float *__restrict__ grad_rgbs = nullptr, const float *__restrict__ extra = nullptr)
 {
     const int lane = tn::lane_id();
     const int64_t ray = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
@@ -122,6 +123,7 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void weights_bwd_kernel(
             grad_rgbs[3 * i] = w * g0; grad_rgbs[3 * i + 1] = w * g1; grad_rgbs[3 * i + 2] = w * g2;
             float d = 0.f;
             if (w != 0.0f) d = rgbs[3 * i] * g0 + rgbs[3 * i + 1] * g1 + rgbs[3 * i + 2] * g2;
+            if constexpr (EXTRA) return (d - gbg) + extra[i];
             return d - gbg;
         } else {
             return grad_w[i];
@@ -312,6 +314,169 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void ray_maps_kernel(
     }
 }
 
+// Distortion loss of Mip-NeRF 360 on packed rays.  For ray r with weights w_k, normalised positions m_k and widths d_k
+//   L = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
+// m increases along a ray, so with the exclusive prefixes W_<i = sum_{j<i} w_j and M_<i = sum_{j<i} w_j m_j
+//   L = 2 sum_i w_i (m_i W_<i - M_<i) + (1/3) sum_i w_i^2 d_i
+//   dL/dw_i = 2 (m_i W_<i - M_<i) + 2 (M_>i - m_i W_>i) + (2/3) w_i d_i.
+// m, d come from the sample's ray parameter t and its step through the warp x = (t - near) / range: m = x, d = step / range
+// (TN_DIST_LINEAR) or m = g(x), d = g'(x) step / range with g(x) = x / 2 below 1 and 1 - 1 / (2 x) from there on (TN_DIST_UNBOUNDED:
+// the inverse of the unbounded marcher's table).  m is taken RELATIVE TO THE RAY'S FIRST SAMPLE (the loss is shift invariant):
+// m W - M cancels, and fp32 prefixes of unshifted positions lose the loss at t ~ 50.  The difference g(x) - g(x_0) is formed in
+// fp64 and rounded once -- behind the knee g flattens like 1 / x^2 and neighbouring fp32 values of g(x) coincide; the prefix
+// sums are fp32 wave scans (wave_scan_add) with carries across 64-sample chunks, a wave per ray like every kernel here.
+struct DistWarp {
+    int32_t warp;
+    float inv_range_f;
+    double near, inv_range;
+};
+
+__device__ __forceinline__ double dist_g(int32_t warp, double x) {
+    return warp == TN_DIST_UNBOUNDED ? (x < 1.0 ? 0.5 * x : 1.0 - 0.5 / x) : x;
+}
+
+// one sample: m (relative to the ray's first sample, g0 = g(x_0)) and the width d
+__device__ __forceinline__ void dist_sample(const DistWarp &p, double g0, float t, float step, float &m, float &d) {
+    const double x = ((double)t - p.near) * p.inv_range;
+    m = (float)(dist_g(p.warp, x) - g0);
+    d = step * p.inv_range_f;
+    if (p.warp == TN_DIST_UNBOUNDED) {
+        const float xf = (float)x;
+        d = x < 1.0 ? 0.5f * d : d / (2.0f * xf * xf);
+    }
+}
+
+// the chunk's inclusive prefixes of w and w m, the carries of the chunks before included
+__device__ __forceinline__ void dist_scan(float w, float m, int lane, float carry_w, float carry_m, float &pw, float &pm) {
+    pw = carry_w + wave_scan_add(w, lane);
+    pm = carry_m + wave_scan_add(w * m, lane);
+}
+
+// Waves stride over the rays so that a block adds to `sum` once (22 000 rays would otherwise queue on one address).
+__global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void distortion_fwd_kernel(
+    const float *__restrict__ weights, const float *__restrict__ t_values, const float *__restrict__ steps, const int32_t *__restrict__ info,
+    int64_t n_rays, DistWarp p, float *__restrict__ loss, double *__restrict__ sum)
+{
+    const int lane = tn::lane_id();
+    const int wave = threadIdx.x >> 6;
+    double wave_total = 0.0;
+    for (int64_t ray = (int64_t)blockIdx.x * WAVES_PER_BLOCK + wave; ray < n_rays; ray += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
+        const int2 sc = reinterpret_cast<const int2 *>(info)[ray];
+        const int start = sc.x, count = sc.y;
+        const double g0 = count > 0 ? dist_g(p.warp, ((double)t_values[start] - p.near) * p.inv_range) : 0.0;
+        float acc = 0.f, cw = 0.f, cm = 0.f;
+        for (int base = 0; base < count; base += 64) {
+            const int k = base + lane;
+            float w = 0.f, m = 0.f, d = 0.f;
+            if (k < count) {
+                w = weights[start + k];
+                dist_sample(p, g0, t_values[start + k], steps[start + k], m, d);
+            }
+            float pw, pm;
+            dist_scan(w, m, lane, cw, cm, pw, pm);
+            float ew = __shfl_up(pw, 1, 64), em = __shfl_up(pm, 1, 64);
+            if (lane == 0) { ew = cw; em = cm; }
+            acc += 2.0f * w * (m * ew - em) + (1.0f / 3.0f) * (w * w) * d;
+            cw = __shfl(pw, 63, 64);
+            cm = __shfl(pm, 63, 64);
+        }
+        acc = tn::wave_sum(acc);
+        if (lane == 0) loss[ray] = acc;
+        wave_total += (double)acc;
+    }
+    if (sum != nullptr) {
+        __shared__ double red[WAVES_PER_BLOCK];
+        if (lane == 0) red[wave] = wave_total;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double s = red[0];
+#pragma unroll
+            for (int i = 1; i < WAVES_PER_BLOCK; ++i) s += red[i];
+            atomicAdd(sum, s);
+        }
+    }
+}
+
+// Rays of up to 64*MAXC samples: w, m, w d and both prefixes stay in registers between the totals pass and the sweep (the form of
+// weights_bwd_kernel); longer rays are read twice.  The totals are the last prefixes themselves, so W_>i and M_>i of a ray's last
+// sample are exactly 0.
+template <int MAXC>
+__global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void distortion_bwd_kernel(
+    const float *__restrict__ weights, const float *__restrict__ t_values, const float *__restrict__ steps, const int32_t *__restrict__ info,
+    int64_t n_rays, DistWarp p, const float *__restrict__ grad_loss, float scale, const float *__restrict__ scale_dev,
+    float *__restrict__ grad_weights)
+{
+    const int lane = tn::lane_id();
+    const int64_t ray = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const int2 sc = reinterpret_cast<const int2 *>(info)[ray];
+    const int start = sc.x, count = sc.y;
+    if (count <= 0) return;
+    float c = scale_dev ? scale * scale_dev[0] : scale;
+    if (grad_loss) c *= grad_loss[ray];
+    const double g0 = dist_g(p.warp, ((double)t_values[start] - p.near) * p.inv_range);
+    // d L / d w of a sample from its prefixes (ew, em: exclusive, pw, pm: inclusive) and the ray's totals
+    auto grad = [&](float m, float wd, float ew, float em, float pw, float pm, float tw, float tm) -> float {
+        return c * (2.0f * ((m * ew - em) + ((tm - pm) - m * (tw - pw))) + (2.0f / 3.0f) * wd);
+    };
+    if (count <= 64 * MAXC) {
+        float ms[MAXC], wd[MAXC], pw[MAXC], pm[MAXC];
+        float cw = 0.f, cm = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < MAXC; ++ch) {
+            ms[ch] = 0.f; wd[ch] = 0.f; pw[ch] = cw; pm[ch] = cm;
+            if (ch * 64 < count) {
+                const int k = ch * 64 + lane;
+                float w = 0.f, d = 0.f;
+                if (k < count) {
+                    w = weights[start + k];
+                    dist_sample(p, g0, t_values[start + k], steps[start + k], ms[ch], d);
+                }
+                wd[ch] = w * d;
+                dist_scan(w, ms[ch], lane, cw, cm, pw[ch], pm[ch]);
+                cw = __shfl(pw[ch], 63, 64);
+                cm = __shfl(pm[ch], 63, 64);
+            }
+        }
+        const float tw = cw, tm = cm;
+        cw = 0.f; cm = 0.f;
+#pragma unroll
+        for (int ch = 0; ch < MAXC; ++ch) {
+            if (ch * 64 < count) {
+                const int k = ch * 64 + lane;
+                float ew = __shfl_up(pw[ch], 1, 64), em = __shfl_up(pm[ch], 1, 64);
+                if (lane == 0) { ew = cw; em = cm; }
+                if (k < count) grad_weights[start + k] = grad(ms[ch], wd[ch], ew, em, pw[ch], pm[ch], tw, tm);
+                cw = __shfl(pw[ch], 63, 64);
+                cm = __shfl(pm[ch], 63, 64);
+            }
+        }
+    } else {
+        float tw = 0.f, tm = 0.f;
+        for (int pass = 0; pass < 2; ++pass) {
+            float cw = 0.f, cm = 0.f;
+            for (int base = 0; base < count; base += 64) {
+                const int k = base + lane;
+                float w = 0.f, m = 0.f, d = 0.f;
+                if (k < count) {
+                    w = weights[start + k];
+                    dist_sample(p, g0, t_values[start + k], steps[start + k], m, d);
+                }
+                float pw, pm;
+                dist_scan(w, m, lane, cw, cm, pw, pm);
+                if (pass == 1) {
+                    float ew = __shfl_up(pw, 1, 64), em = __shfl_up(pm, 1, 64);
+                    if (lane == 0) { ew = cw; em = cm; }
+                    if (k < count) grad_weights[start + k] = grad(m, w * d, ew, em, pw, pm, tw, tm);
+                }
+                cw = __shfl(pw, 63, 64);
+                cm = __shfl(pm, 63, 64);
+            }
+            tw = cw; tm = cm;
+        }
+    }
+}
+
 inline unsigned ray_blocks(int64_t n_rays) { return (unsigned)((n_rays + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
 
 }  // namespace
@@ -376,6 +541,62 @@ extern "C" int tn_render_rays_bwd(const float *sigmas, const float *steps, const
     weights_bwd_kernel<16, true><<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(
         sigmas, steps, info, weights, nullptr, grad_sigmas, n_rays, rgbs, bg, grad_rendered, grad_rgbs);
     return tn::check_launch("weights_bwd_kernel(composite)");
+}
+
+static int dist_warp(const char *fn, int32_t warp, float near, float range, DistWarp *p)
+{
+    if (!(warp == TN_DIST_LINEAR || warp == TN_DIST_UNBOUNDED) || !(range > 0.0f)) {
+        tn::set_error("%s: unknown warp or range <= 0", fn);
+        return TN_E_CONFIG;
+    }
+    p->warp = warp;
+    p->near = (double)near;
+    p->inv_range = 1.0 / (double)range;
+    p->inv_range_f = (float)p->inv_range;
+    return TN_OK;
+}
+
+extern "C" int tn_distortion_fwd(const float *weights, const float *t_values, const float *steps, const int32_t *info, int64_t n_rays,
+                                 int32_t warp, float near, float range, float *loss, double *sum, void *stream)
+{
+    TN_REQUIRE(n_rays >= 0, TN_E_SIZE, "tn_distortion_fwd: negative size");
+    if (n_rays == 0) return TN_OK;
+    TN_REQUIRE(weights && t_values && steps && info && loss, TN_E_NULL, "tn_distortion_fwd: null pointer");
+    DistWarp p;
+    if (int rc = dist_warp("tn_distortion_fwd", warp, near, range, &p)) return rc;
+    TN_REQUIRE(((uintptr_t)info & 7) == 0, TN_E_ALIGN, "tn_distortion_fwd: info must be 8-byte aligned");
+    const unsigned blocks = std::min(ray_blocks(n_rays), 2048u);
+    distortion_fwd_kernel<<<dim3(blocks), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(weights, t_values, steps, info, n_rays, p, loss, sum);
+    return tn::check_launch("distortion_fwd_kernel");
+}
+
+extern "C" int tn_distortion_bwd(const float *weights, const float *t_values, const float *steps, const int32_t *info, int64_t n_rays,
+                                 int32_t warp, float near, float range, const float *grad_loss, float scale, const float *scale_dev,
+                                 float *grad_weights, void *stream)
+{
+    TN_REQUIRE(n_rays >= 0, TN_E_SIZE, "tn_distortion_bwd: negative size");
+    if (n_rays == 0) return TN_OK;
+    TN_REQUIRE(weights && t_values && steps && info && grad_weights, TN_E_NULL, "tn_distortion_bwd: null pointer");
+    DistWarp p;
+    if (int rc = dist_warp("tn_distortion_bwd", warp, near, range, &p)) return rc;
+    TN_REQUIRE(((uintptr_t)info & 7) == 0, TN_E_ALIGN, "tn_distortion_bwd: info must be 8-byte aligned");
+    distortion_bwd_kernel<8><<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(
+        weights, t_values, steps, info, n_rays, p, grad_loss, scale, scale_dev, grad_weights);
+    return tn::check_launch("distortion_bwd_kernel");
+}
+
+extern "C" int tn_render_rays_bwd_dw(const float *sigmas, const float *steps, const float *rgbs, const int32_t *info, const float *bg,
+                                     const float *weights, const float *grad_rendered, const float *grad_weights_extra, float *grad_rgbs,
+                                     float *grad_sigmas, int64_t n_samples, int64_t n_rays, void *stream)
+{
+    TN_REQUIRE(n_samples >= 0 && n_rays >= 0, TN_E_SIZE, "tn_render_rays_bwd_dw: negative size");
+    if (n_rays == 0 || n_samples == 0) return TN_OK;
+    TN_REQUIRE(sigmas && steps && rgbs && info && weights && grad_rendered && grad_weights_extra && grad_rgbs && grad_sigmas, TN_E_NULL,
+               "tn_render_rays_bwd_dw: null pointer");
+    TN_REQUIRE(((uintptr_t)info & 7) == 0, TN_E_ALIGN, "tn_render_rays_bwd_dw: info must be 8-byte aligned");
+    weights_bwd_kernel<16, true, true><<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(
+        sigmas, steps, info, weights, nullptr, grad_sigmas, n_rays, rgbs, bg, grad_rendered, grad_rgbs, grad_weights_extra);
+    return tn::check_launch("weights_bwd_kernel(composite, extra)");
 }
 
 extern "C" int tn_weights_bwd(const float *sigmas, const float *steps, const int32_t *info, const float *weights,

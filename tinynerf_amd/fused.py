@@ -161,6 +161,9 @@ class _Call:
     hint: Optional[dict]        # run.Trainer.build_batch's _batch_aux
     stats: Optional[dict]       # the renderer's _stats
     link: Optional[dict] = None     # _RenderHeads: row views offered by the wide stack that produced feat
+    # NerfRenderer.render_with_distortion: {"t": [n], "warp": (warp, near, range)} -- the node hands out the per-ray distortion loss of
+    # its weights as a second output; the trainer adds {"sum": fp64 [1] accumulator, "scale": constant upstream gradient}
+    dist: Optional[dict] = None
 
     def split(self, params: Sequence[torch.Tensor]) -> Tuple[List[torch.Tensor], List[torch.Tensor], List[torch.Tensor]]:
         k = self.n_planes + self.n_sigma
@@ -328,6 +331,17 @@ def _composite(ctx: Any, a: _Call, covered: bool, dev: torch.device, sigma, step
     return out, weights
 
 
+def _distortion(ctx: Any, a: _Call, dev: torch.device, weights, steps, info):
+    """the node's second output (a.dist): per-ray distortion loss of the weights the composite used, one launch (tn_distortion_fwd)"""
+    ctx.set_materialize_grads(False)          # an output the caller never uses sends None, not a tensor of zeros, to the backward
+    R = info.size(0)
+    loss = torch.empty(R, device=dev)
+    warp, near, rng = a.dist["warp"]
+    L.call("tn_distortion_fwd", dev, L.ptr(weights), L.ptr(a.dist["t"]), L.ptr(steps), L.ptr(info), C.c_int64(R), C.c_int32(warp),
+           C.c_float(near), C.c_float(rng), L.ptr(loss), L.ptr(a.dist.get("sum")))
+    return loss
+
+
 def _grad_buffers(ctx: Any, params: Sequence[torch.Tensor]) -> Tuple[List[torch.Tensor], List[Optional[torch.Tensor]]]:
     """where the kernels write each parameter's gradient -- param.grad itself when the caller accumulates into it and it has the
     parameter's layout, a zeroed tensor otherwise -- and what the backward returns to autograd (None for the former)"""
@@ -353,8 +367,13 @@ def _heads_bwd(dev: torch.device, pair: bool, rdesc, sdesc, feat, table, g_rgbs,
     L.call("tn_mlp_bwd", dev, C.byref(sdesc), L.ptr(feat), C.c_void_p(None), L.ptr(g_sigma), n, *gw[2:], L.ptr(g_feat), L.ptr(ws_s), C.c_int64(sb))
 
 
-def _rays_bwd(ctx: Any, grad_out: torch.Tensor, sigma, steps, rgbs, info, bg, weights) -> Tuple[torch.Tensor, torch.Tensor]:
-    """composite -> (rgbs, weights) and weights -> sigma as one launch per ray (the weights' gradient needs only the composite's)"""
+def _rays_bwd(ctx: Any, grad_out: Optional[torch.Tensor], sigma, steps, rgbs, info, bg, weights,
+              grad_dist: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """composite -> (rgbs, weights) and weights -> sigma as one launch per ray (the weights' gradient needs only the composite's).
+    With a distortion output in use its gradient w.r.t. the weights (tn_distortion_bwd) joins the composite's inside that launch
+    (tn_render_rays_bwd_dw)."""
+    if grad_out is None:                     # (only the distortion output was used)
+        grad_out = torch.zeros((info.size(0), 3), device=sigma.device)
     g_out = grad_out.contiguous()
     # "Empty iteration": zero gradients, as on the module-by-module path.  Applied here unless the caller has DECLARED the upstream
     # gradient gated (run.Trainer.step_on_batch sets stats["upstream_gated"] around tn_mse_grad_gated): any other loss on a
@@ -366,8 +385,22 @@ def _rays_bwd(ctx: Any, grad_out: torch.Tensor, sigma, steps, rgbs, info, bg, we
     g_sigma = _alloc(ctx.call.arena, "g_sigma", (n,), dev)
     if not ctx.plan.covered:     # samples no ray owns: zero gradient, not whatever the arena held (the kernel writes every
         g_rgbs.zero_(); g_sigma.zero_()      # sample a ray owns)
-    L.call("tn_render_rays_bwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), L.ptr(weights),
-           L.ptr(g_out), L.ptr(g_rgbs), L.ptr(g_sigma), C.c_int64(n), C.c_int64(R))
+    dist = ctx.call.dist
+    scale = dist.get("scale") if dist is not None else None       # the trainer's hand-written upstream gradient: a constant per ray
+    if dist is None or (scale is None and grad_dist is None):
+        L.call("tn_render_rays_bwd", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), L.ptr(weights),
+               L.ptr(g_out), L.ptr(g_rgbs), L.ptr(g_sigma), C.c_int64(n), C.c_int64(R))
+        return g_rgbs, g_sigma
+    # (in an "Empty iteration" every w is 0 and so is d L / d w: no gate here)
+    g_extra = _alloc(ctx.call.arena, "g_weights_dist", (n,), dev)
+    if not ctx.plan.covered:
+        g_extra.zero_()
+    warp, near, rng = dist["warp"]
+    g_dist = None if scale is not None else grad_dist.contiguous()
+    L.call("tn_distortion_bwd", dev, L.ptr(weights), L.ptr(dist["t"]), L.ptr(steps), L.ptr(info), C.c_int64(R), C.c_int32(warp),
+           C.c_float(near), C.c_float(rng), L.ptr(g_dist), C.c_float(1.0 if scale is None else scale), C.c_void_p(None), L.ptr(g_extra))
+    L.call("tn_render_rays_bwd_dw", dev, L.ptr(sigma), L.ptr(steps), L.ptr(rgbs), L.ptr(info), L.ptr(bg), L.ptr(weights),
+           L.ptr(g_out), L.ptr(g_extra), L.ptr(g_rgbs), L.ptr(g_sigma), C.c_int64(n), C.c_int64(R))
     return g_rgbs, g_sigma
 
 
@@ -413,15 +446,17 @@ class _RenderKPlanes(Function):
         ctx.save_for_backward(packed, info, bg, freqs, feat, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params)
         ctx.call, ctx.plan, ctx.planes_ready = a, p, ready
         ctx.param_refs = params if a.accumulate else None
+        if a.dist is not None:
+            return out, _distortion(ctx, a, dev, weights, steps, info)
         return out
 
     @staticmethod
-    def backward(ctx: Any, grad_out: torch.Tensor):  # type: ignore
+    def backward(ctx: Any, grad_out: torch.Tensor, grad_dist: Optional[torch.Tensor] = None):  # type: ignore
         packed, info, bg, freqs, feat, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params = ctx.saved_tensors
         a, p = ctx.call, ctx.plan
         planes, sig_p, rgb_p = a.split(params)
         dev, n, F = packed.device, packed.size(0), feat.size(1)
-        g_rgbs, g_sigma = _rays_bwd(ctx, grad_out, sigma, steps, rgbs, info, bg, weights)
+        g_rgbs, g_sigma = _rays_bwd(ctx, grad_out, sigma, steps, rgbs, info, bg, weights, grad_dist)
         grads, returned = _grad_buffers(ctx, params)
         g_planes, k = grads[:a.n_planes], a.n_planes + a.n_sigma
         gw = _grad_ptrs(grads[a.n_planes:k], grads[k:])
@@ -549,15 +584,17 @@ class _RenderHeads(Function):
         ctx.save_for_backward(feat, info, bg, freqs, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params)
         ctx.call, ctx.plan, ctx.link = a, p, link
         ctx.param_refs = params if a.accumulate else None
+        if a.dist is not None:
+            return out, _distortion(ctx, a, dev, weights, steps, info)
         return out
 
     @staticmethod
-    def backward(ctx: Any, grad_out: torch.Tensor):  # type: ignore
+    def backward(ctx: Any, grad_out: torch.Tensor, grad_dist: Optional[torch.Tensor] = None):  # type: ignore
         feat, info, bg, freqs, sigma, steps, table, ray_ids, weights, rgbs, ws_s, ws_r, *params = ctx.saved_tensors
         a, p, link = ctx.call, ctx.plan, ctx.link
         _, sig_p, rgb_p = a.split(params)
         dev, (n, F) = feat.device, feat.shape
-        g_rgbs, g_sigma = _rays_bwd(ctx, grad_out, sigma, steps, rgbs, info, bg, weights)
+        g_rgbs, g_sigma = _rays_bwd(ctx, grad_out, sigma, steps, rgbs, info, bg, weights, grad_dist)
         grads, returned = _grad_buffers(ctx, params)
         gw = _grad_ptrs(grads[:a.n_sigma], grads[a.n_sigma:])
         # with row views the heads write d loss / d feat straight into the feature stack's workspace (rows) and read feat^T from
@@ -620,8 +657,9 @@ def supports(renderer) -> bool:
     return True
 
 
-def render(renderer, packed: torch.Tensor, info: torch.Tensor, thr: float, accumulate_into_grad: bool = False) -> torch.Tensor:
-    """Fused forward of ``renderer`` on packed samples (see supports())."""
+def render(renderer, packed: torch.Tensor, info: torch.Tensor, thr: float, accumulate_into_grad: bool = False, dist: Optional[dict] = None):
+    """Fused forward of ``renderer`` on packed samples (see supports()).  ``dist`` (NerfRenderer.render_with_distortion): t and the
+    warp -- the result is then (rgb, per-ray distortion loss)."""
     from .models import KPlanesFeatureField
     fm, sd, cd = renderer.feature_module, renderer.sigma_decoder, renderer.rgb_decoder
     sig_p, rgb_p = sd.net.params(), cd.net.params()
@@ -630,10 +668,15 @@ def render(renderer, packed: torch.Tensor, info: torch.Tensor, thr: float, accum
     if getattr(renderer, "reuse_buffers", False):
         arena = renderer.__dict__.setdefault("_arena", Arena())
     hint, stats = getattr(renderer, "_batch_aux", None), renderer.__dict__.setdefault("_stats", {})
+    if dist is not None:
+        train_side = stats.get("dist_train")       # the trainer's accumulator slot and constant upstream gradient
+        if train_side is not None:
+            dist = {**dist, **train_side}
+            train_side["taken"] = True
     if isinstance(fm, KPlanesFeatureField):
         planes = fm.plane_tensors()
         train = torch.is_grad_enabled() and any(p.requires_grad for p in (*planes, *sig_p, *rgb_p))
-        a = _Call(float(thr), cd.n_freqs, len(planes), len(sig_p), accumulate_into_grad, arena, train, hint, stats)
+        a = _Call(float(thr), cd.n_freqs, len(planes), len(sig_p), accumulate_into_grad, arena, train, hint, stats, dist=dist)
         return _RenderKPlanes.apply(a, packed.contiguous(), info.contiguous(), bg, cd.pe.freqs, *planes, *sig_p, *rgb_p)
     # harness: the stack whose row view this node matched last time may leave its output as rows only (TN_MLP_ROWS_ONLY) -- armed for
     # exactly this forward; _RenderHeads fails loudly if it then cannot read the rows
@@ -673,5 +716,5 @@ def render(renderer, packed: torch.Tensor, info: torch.Tensor, thr: float, accum
         wc, bc, ws_, bs_ = _MergeLast.apply(accumulate_into_grad, pe, rgb_p[0], rgb_p[1], sig_p[0], sig_p[1], w_last, b_last)
         rgb_p = [wc, bc, *rgb_p[2:]]
         sig_p = [ws_, bs_, *sig_p[2:]]
-    a = _Call(float(thr), cd.n_freqs, 0, len(sig_p), accumulate_into_grad, arena, train, hint, stats, link)
+    a = _Call(float(thr), cd.n_freqs, 0, len(sig_p), accumulate_into_grad, arena, train, hint, stats, link, dist)
     return _RenderHeads.apply(a, feat, packed.contiguous(), info.contiguous(), bg, cd.pe.freqs, *sig_p, *rgb_p)

@@ -25,7 +25,7 @@ import torch
 
 from . import _lib as L
 from .core import (ContractionAABB, ContractionMip360, NerfRenderer, OccupancyGrid, RayMarcherAABB,
-                   RayMarcherUnbounded, RayProvider)
+                   RayMarcherUnbounded, RayProvider, distortion_warp)
 from .optim import FusedAdam
 from .models import (CobafaFeatureField, KPlanesFeatureField, VanillaColorDecoder, VanillaFeatureMLP,
                      VanillaOpacityDecoder)
@@ -68,6 +68,10 @@ class TrainConfig:
     # (weight decay and the regulariser change dead rows too).  None: on when the recipe's batch is split over >= 4 ranks (shard >= 4:
     # DESIGN 5.1 -- below ~1.1 ms of compute per step the replicated optimizer pass is what limits strong scaling).
     sharded_optimizer: Optional[bool] = None
+    # > 0: the distortion loss of Mip-NeRF 360 on the step's weights (core.RayDistortion) joins the loss as
+    # distortion_weight * mean over the step's rays, in the marcher's normalised ray parameter (core.distortion_warp).  Mip-NeRF 360 and
+    # K-Planes use 0.01 and 0.001.  0: the step is the recipe's, launch for launch.  Single GPU only for now.
+    distortion_weight: float = 0.0
 
 
 def jitter_seed(seed: int, batch_no: int, rank: int = 0) -> int:
@@ -133,6 +137,11 @@ class Trainer:
             raise ValueError(f"TrainConfig.shard = {cfg.shard} must divide batch_size = {cfg.batch_size}")
         self.loader_batch = cfg.batch_size // cfg.shard              # rays per loader batch ON THIS RANK
         self.target_sample_size = self.loader_batch * cfg.n_samples
+        if cfg.distortion_weight < 0:
+            raise ValueError(f"TrainConfig.distortion_weight = {cfg.distortion_weight} must be >= 0")
+        if cfg.distortion_weight > 0 and world_size > 1:
+            raise ValueError("TrainConfig.distortion_weight > 0 is single-GPU for now: the mean over ALL ranks' rays is not exchanged yet")
+        self.renderer.distortion_warp = distortion_warp(self.ray_provider.ray_marcher)
         params = list(self.renderer.parameters())
         for p in params:                                # grads keep the parameter's (channels_last) layout
             p.grad = torch.zeros_like(p)
@@ -194,7 +203,8 @@ class Trainer:
         self._side2: Optional[torch.cuda.Stream] = None          # TN_ADAM_OVERLAP: the planes' optimizer pass
         self._gate_ring = torch.zeros(256, device=device)
         self._gate_tick = 0
-        self._acc_ring = torch.zeros((64, 1 + 32 * 3), dtype=torch.float64, device=device)
+        self._acc_ring = torch.zeros((64, 1 + 32 * 3 + 1), dtype=torch.float64, device=device)     # (the last slot: the distortion sum)
+        self._batch_t: Optional[torch.Tensor] = None      # distortion_weight > 0: ray parameter of every sample of the batch last built
         self._acc_tick = 0               # a counter of its own (train_step may be assigned from outside, a step may be retried)
         self.prefetch = True
         # tensors that a sampler pass in flight on the side stream may still read although the trainer has dropped them (the
@@ -341,8 +351,14 @@ class Trainer:
         packed = self._buf("packed", (n, 7), torch.float32)
         ray_ids = self._buf("ray_ids", (n,), torch.int32)
         steps = self._buf("steps", (n,), torch.float32)
-        L.call("tn_sample_pack", dev, C.byref(pend["desc"]), L.ptr(pend["o"]), L.ptr(pend["d"]), C.c_int64(R), L.ptr(pend["maskbits"]),
-               L.ptr(info), C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), L.ptr(steps), C.c_int64(n))
+        t = None
+        if self.cfg.distortion_weight > 0:        # the distortion loss needs the ray parameter of every sample: the same kernel writes it out
+            t = self._buf("t_values", (n,), torch.float32)
+            L.call("tn_sample_pack_t", dev, C.byref(pend["desc"]), L.ptr(pend["o"]), L.ptr(pend["d"]), C.c_int64(R), L.ptr(pend["maskbits"]),
+                   L.ptr(info), C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), L.ptr(steps), L.ptr(t), C.c_int64(n))
+        else:
+            L.call("tn_sample_pack", dev, C.byref(pend["desc"]), L.ptr(pend["o"]), L.ptr(pend["d"]), C.c_int64(R), L.ptr(pend["maskbits"]),
+                   L.ptr(info), C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), L.ptr(steps), C.c_int64(n))
         # what the fused render node would otherwise rebuild from (packed, info): ray id and step of every sample, ray directions
         # "Empty iteration" flag of this step: one slot of a ring that is zeroed once per lap (the weights kernel only raises it)
         slot = self._gate_tick % self._gate_ring.numel()          # (a counter of its own: a batch may be built without a step)
@@ -352,6 +368,7 @@ class Trainer:
         self.renderer._batch_aux = {"key": (packed.data_ptr(), n, R), "ray_ids": ray_ids, "steps": steps, "dirs": pend["d"][:R],
                                     "planes_ready": self._planes_ready if self.world > 1 else (self._planes_adam_early if ADAM_OVERLAP else None),
                                     "gate": self._gate_ring[slot:slot + 1]}
+        self._batch_t = t
         return packed, info, pend["rgb"][:R], k
 
     # ------------------------------------------------------------------ one optimizer step
@@ -360,12 +377,15 @@ class Trainer:
 
     def step(self) -> Dict[str, float]:
         packed, info, target, k = self.build_batch()
-        return self.step_on_batch(packed, info, target, k)
+        return self.step_on_batch(packed, info, target, k, t=self._batch_t)
 
     def step_on_batch(self, packed: torch.Tensor, info: torch.Tensor, target: torch.Tensor, k: int = 0,
-                      prefetch: Optional[bool] = None) -> Dict[str, float]:
-        """Everything of one optimizer step behind the dynamic batch (run.py:246-261) on an explicit batch."""
+                      prefetch: Optional[bool] = None, t: Optional[torch.Tensor] = None) -> Dict[str, float]:
+        """Everything of one optimizer step behind the dynamic batch (run.py:246-261) on an explicit batch.  ``t`` [N]: the ray
+        parameter of every packed sample (``RayProvider(..., return_t=True)``), needed when ``cfg.distortion_weight > 0``."""
         cfg = self.cfg
+        if cfg.distortion_weight > 0 and t is None:
+            raise ValueError("TrainConfig.distortion_weight > 0: step_on_batch needs t, the ray parameter of every packed sample")
         self.renderer.train()
         if self.train_step % self.occupancy_grid_updates == 0:                    # run.py:248-249
             jit = None
@@ -379,7 +399,23 @@ class Trainer:
         if self.world > 1:                 # global ray count of the step (see global_ray_count): travels during the forward pass
             ray_count = torch.full((1,), float(info.size(0)), device=self.device)
             ray_count_done = torch.distributed.all_reduce(ray_count, async_op=True)
-        rendered = self.renderer(packed, info)                                    # run.py:251
+        acc, dist_side = None, None
+        if cfg.distortion_weight > 0:
+            acc = self._next_acc_row()       # (ahead of the forward pass: the render node adds the distortion sum to it)
+            # + distortion_weight * mean_r L_r, scaled like the rest; as for the MSE the gradient is written by hand: the render node adds
+            # the per-ray losses into the accumulator row and, in its backward, takes a constant upstream gradient (no second output
+            # through autograd, no fill launch)
+            dist_side = {"sum": acc[-1:], "scale": cfg.distortion_weight * cfg.grad_scale / max(info.size(0), 1)}
+            stats0 = self.renderer.__dict__.setdefault("_stats", {})
+            stats0["dist_train"] = dist_side
+            try:
+                rendered, _ = self.renderer.render_with_distortion(packed, info, t)
+            finally:
+                stats0.pop("dist_train", None)
+            if not dist_side.get("taken"):
+                raise RuntimeError("tinynerf_amd: distortion_weight > 0 needs a renderer the fused render nodes take (fused.supports)")
+        else:
+            rendered = self.renderer(packed, info)                                # run.py:251
         # "Empty iteration" (core.py:251-254): no sample of the step has w > 0 -> no parameter is reached by the image loss, and
         # torch.optim.Adam skips the grad-is-None parameters (run.py:258-260); decided on the device through this scalar (the
         # step's largest weight, the tensor the render node's backward reads).  N > 1: the step on the union of all ranks' rays
@@ -407,12 +443,8 @@ class Trainer:
         # by hand (4 small kernels instead of ~12 through autograd); the regulariser's value and gradient are one launch.
         # (gradients were zeroed by the previous optimizer pass: zero_grad -> backward -> step, run.py:258-260)
         R = rendered.size(0)
-        # [0]: sum of squares, [1:]: regulariser sums -- one row of a ring that is zeroed once per lap (no fill launch per step)
-        row = self._acc_tick % self._acc_ring.size(0)
-        self._acc_tick += 1
-        if row == 0:
-            self._acc_ring.zero_()
-        acc = self._acc_ring[row]
+        if acc is None:
+            acc = self._next_acc_row()
         grad = self._buf("grad_rendered", (R, 3), torch.float32)
         if self.world == 1:
             inv, inv_dev = 1.0 / (3.0 * R), None
@@ -434,7 +466,7 @@ class Trainer:
         self._early_adam = None
         if ADAM_OVERLAP and self.world == 1 and cfg.method == "kplanes" and self.grad_hook is None:
             spec0, _ = self.renderer.feature_module.regulariser_spec(self.tv_reg_alpha, self.l1_reg_alpha)   # type: ignore
-            self._early_adam = {"plane_reg": {"spec": spec0, "upstream": cfg.grad_scale, "sums": acc[1:]}, "gate": gate, "done": False}
+            self._early_adam = {"plane_reg": {"spec": spec0, "upstream": cfg.grad_scale, "sums": acc[1:-1]}, "gate": gate, "done": False}
         early_done = False
         try:
             rendered.backward(grad)
@@ -451,10 +483,11 @@ class Trainer:
             # the regulariser's gradient is the same on every rank (same planes): it is folded into the optimizer pass, after
             # the gradient exchange, with its full weight (grad_scale: the loss is scaled and never unscaled)
             spec, reg_coef = self.renderer.feature_module.regulariser_spec(self.tv_reg_alpha, self.l1_reg_alpha)   # type: ignore
-            plane_reg = {"spec": spec, "upstream": cfg.grad_scale, "sums": acc[1:]}
+            plane_reg = {"spec": spec, "upstream": cfg.grad_scale, "sums": acc[1:-1]}
             if self._sharded:                # this rank's rows of every plane: the only ones its optimizer pass touches
                 plane_reg["rows"] = {id(p): Trainer._own_rows(p.size(2), self.rank, self.world) for p in self.renderer.feature_module.plane_tensors()}
         self._loss_parts = (acc, inv, inv_dev, reg_coef)
+        self._loss_dist = cfg.distortion_weight / max(R, 1) if dist_side is not None else None
         if self.world > 1:
             self.all_reduce_grads(gate)
         if self.grad_hook is not None:
@@ -474,6 +507,15 @@ class Trainer:
         self.train_step += 1
         self.last = {"n_samples": float(packed.size(0)), "n_rays": float(info.size(0)), "k": float(k)}
         return self.last
+
+    def _next_acc_row(self) -> torch.Tensor:
+        """the step's accumulators -- [0]: sum of squares, [1:-1]: regulariser sums, [-1]: distortion sum -- one row of a ring that is
+        zeroed once per lap (no fill launch per step)"""
+        row = self._acc_tick % self._acc_ring.size(0)
+        self._acc_tick += 1
+        if row == 0:
+            self._acc_ring.zero_()
+        return self._acc_ring[row]
 
     def global_ray_count(self, local_rays: int, gate: Optional[torch.Tensor] = None):
         """MSE over ALL ranks' rays: sum of local squared errors / (3 * global ray count).  Dynamic batches
@@ -495,12 +537,14 @@ class Trainer:
         return ((rendered - target) ** 2).sum() / (3.0 * Trainer.global_ray_count(self, rendered.size(0)))
 
     def loss_device(self) -> torch.Tensor:
-        """Loss of the last step (MSE + weighted regulariser, run.py:252-256) as a 1-element device tensor, assembled
+        """Loss of the last step (MSE + weighted regulariser, run.py:252-256, + the weighted distortion term) as a 1-element device tensor, assembled
         from the accumulators the step left behind (valid until the next step); no host sync."""
         acc, inv, inv_dev, reg_coef = self._loss_parts
         v = acc[0] * inv * (inv_dev[0].double() if inv_dev is not None else 1.0)
         if reg_coef is not None:                  # (every rank holds the full sums -- or, sharded optimizer pass, its rows' share of them)
             v = v + (acc[1:1 + reg_coef.numel()] * reg_coef.reshape(-1)).sum() / (1 if getattr(self, "_sharded", False) else self.world)
+        if getattr(self, "_loss_dist", None) is not None:
+            v = v + acc[-1] * self._loss_dist
         v = v.float().reshape(1).clone()
         if self.world > 1:
             torch.distributed.all_reduce(v)

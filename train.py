@@ -10,7 +10,7 @@ import random
 import uuid
 from pathlib import Path
 
-# (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps and --render_maps
+# (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps and --distortion_weight
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -24,6 +24,7 @@ FLAGS = (
     ("--eval_n", dict(type=int, default=1, help="number of images to evaluate on")),
     ("--max_steps", dict(type=int, default=None, help="stop early (the recipe's step count is 2048*4096/batch_size)")),
     ("--render_maps", dict(action="store_true", help="the final test render also writes depth / opacity maps")),
+    ("--distortion_weight", dict(type=float, default=0.0, help="weight of the Mip-NeRF 360 distortion loss (0: off; 1e-3 .. 1e-2 is usual)")),
 )
 
 
@@ -72,7 +73,8 @@ def main(argv=None):
         raise FileNotFoundError(root / "transforms_train.json")
     run_dir = fresh_run_dir(Path(args.output), args)
     print(f"Experiment saved to {run_dir}")
-    cfg = TrainConfig(method=args.method, scene_type=args.scene_type, batch_size=args.batch_size, n_samples=args.n_samples, seed=seed)
+    cfg = TrainConfig(method=args.method, scene_type=args.scene_type, batch_size=args.batch_size, n_samples=args.n_samples, seed=seed,
+                      distortion_weight=args.distortion_weight)
     train(cfg, train_rays, load_split(data, root, "val", device, rays=False), load_split(data, root, "test", device, rays=False),
           run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps)
 
