@@ -561,6 +561,20 @@ int tn_distortion_bwd(const float *weights, const float *t_values, const float *
 int tn_render_rays_bwd_dw(const float *sigmas, const float *steps, const float *rgbs, const int32_t *info, const float *bg,
                           const float *weights, const float *grad_rendered, const float *grad_weights_extra, float *grad_rgbs,
                           float *grad_sigmas, int64_t n_samples, int64_t n_rays, void *stream);
+/* Single-scale SSIM (Wang et al. 2004) of two images a, b: fp32 [H, W, C] channel last, 1 <= C <= 4, in the form of the NeRF
+ * evaluation scripts: 11 x 11 window w(i,j) = g(i) g(j), g(i) = exp(-(i-5)^2 / (2 * 1.5^2)) / sum (fp64, rounded to fp32 once);
+ * one value per window that lies wholly inside the image ("valid", no padding) and per channel -> a map of [(H-10), (W-10), C]:
+ *   mu_a = sum w a, var_a = sum w (a - mu_a)^2, cov = sum w (a - mu_a)(b - mu_b), c1 = (0.01 L)^2, c2 = (0.03 L)^2, L = data_range
+ *   ssim = (2 mu_a mu_b + c1)(2 cov + c2) / ((mu_a^2 + mu_b^2 + c1)(var_a + var_b + c2))
+ * mean[0] (device) = plain mean of the map; `map` may be NULL (not written).  Centred moments in fp32 (two passes over the window
+ * from LDS): every map entry within 1e-5 of an fp64 evaluation.  Two launches: tiles of 32 x 8 windows write fp64 partial sums into
+ * `workspace` (tn_ssim_workspace_bytes, 8-byte aligned), one workgroup adds them in a fixed order -- no atomics, the same bits on
+ * every call, with or without `map`.  TN_E_SIZE: a negative size or a side above 65536; TN_E_CONFIG: H < 11, W < 11, C outside
+ * 1..4, data_range not a finite number > 0, workspace too small.  No reference call site: the reference's EvalMetrics.ssim is a
+ * placeholder that stays 0 (run.py:56-60). */
+int tn_ssim_workspace_bytes(int64_t H, int64_t W, int32_t C, int64_t *bytes);          /* host only */
+int tn_ssim(const float *a, const float *b, int64_t H, int64_t W, int32_t C, float data_range, float *map, void *workspace,
+            int64_t workspace_bytes, float *mean, void *stream);
 /* The harness' batch draw (run.py:225-229, the DataLoader's index_select): rows idx[i] of the [N, 3] ray tables -> out_* [n, 3]
  * in one launch; rgbs / out_rgb may be NULL. */
 int tn_gather_rays(const float *rays_o, const float *rays_d, const float *rgbs, const int32_t *idx, int64_t n,

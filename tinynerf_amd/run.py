@@ -36,6 +36,34 @@ def psnr(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return -10. * torch.log10(torch.mean((x - y) ** 2))
 
 
+def ssim(x: torch.Tensor, y: torch.Tensor, data_range: float = 1.0, return_map: bool = False):
+    """Single-scale SSIM of two float32 [H, W, C] device images (C <= 4; what ``infer`` returns and ``dataset[i]["rgbs"]`` holds) as
+    the NeRF evaluation scripts compute it: 11 x 11 Gaussian window (sigma 1.5), windows wholly inside the image, mean over windows
+    and channels (``tn_ssim``).  Returns a 0-dim device tensor -- no host sync -- and with ``return_map`` also the
+    [(H-10), (W-10), C] map."""
+    if x.dim() != 3 or x.shape != y.shape:
+        raise RuntimeError("ssim: x and y must be [H, W, C] images of the same shape")
+    if x.dtype != torch.float32 or y.dtype != torch.float32:
+        raise RuntimeError("ssim: x and y must be float32")
+    dev = L.require_cuda(x, y)
+    H, W, Cn = x.shape
+    if H < 11 or W < 11 or not 1 <= Cn <= 4:
+        raise RuntimeError("ssim: needs H >= 11, W >= 11 (one whole 11 x 11 window) and 1 <= C <= 4")
+    if not float(data_range) > 0.0:
+        raise ValueError("ssim: data_range must be > 0")
+    nbytes = C.c_int64(0)
+    L.call_plain("tn_ssim_workspace_bytes", C.c_int64(H), C.c_int64(W), C.c_int32(Cn), C.byref(nbytes))
+    workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    mean = torch.empty((), dtype=torch.float32, device=dev)
+    smap = torch.empty((H - 10, W - 10, Cn), dtype=torch.float32, device=dev) if return_map else None
+    L.call("tn_ssim", dev, L.ptr(x), L.ptr(y), C.c_int64(H), C.c_int64(W), C.c_int32(Cn), C.c_float(data_range), L.ptr(smap),
+           L.ptr(workspace), C.c_int64(nbytes.value), L.ptr(mean))
+    return (mean, smap) if return_map else mean
+
+
+_image_ssim = ssim          # evaluate() and train() take a flag of that name
+
+
 from .config import CONFIG as _CONFIG      # noqa: E402
 ADAM_OVERLAP = _CONFIG.adam_overlap      # TN_ADAM_OVERLAP; N == 1: the planes' optimizer pass beside the weight-gradient kernels (_planes_adam_early)
 SIDE_PLAN = _CONFIG.side_plan            # TN_SIDE_PLAN; the next step's sampler pass on a stream of its own
@@ -813,7 +841,7 @@ class Trainer:
 class EvalMetrics:
     mse_loss: float = 0.
     psnr: float = 0.
-    ssim: float = 0.          # never computed by the reference either (run.py:56-60)
+    ssim: float = 0.          # a placeholder in the reference (run.py:56-60); filled by evaluate(ssim=True) / train.py --ssim, else 0.0
 
 
 @torch.no_grad()
@@ -860,20 +888,25 @@ def _save_maps(res: Dict[str, torch.Tensor], folder, name: str, i: int) -> None:
     np.savez(folder / f"{name}_maps_{i:04d}.npz", depth_scale=np.float32(scale), **host)
 
 
-def evaluate(dataset, rendered: List[torch.Tensor], indices: List[int]) -> List[EvalMetrics]:
-    """run.py:62-76."""
+def evaluate(dataset, rendered: List[torch.Tensor], indices: List[int], ssim: bool = False) -> List[EvalMetrics]:
+    """run.py:62-76.  ``ssim``: also fill ``EvalMetrics.ssim`` (``run.ssim`` of the float images, data_range 1); off, the field
+    stays 0.0 as in the reference and nothing else is launched."""
     res = []
     for i, img in zip(indices, rendered):
         true = dataset[i]["rgbs"].to(img.device)
-        res.append(EvalMetrics(mse_loss=torch.nn.functional.mse_loss(true, img).item(), psnr=psnr(true, img).item()))
+        m = EvalMetrics(mse_loss=torch.nn.functional.mse_loss(true, img).item(), psnr=psnr(true, img).item())
+        if ssim:
+            m.ssim = _image_ssim(true.float().contiguous(), img.float().contiguous()).item()
+        res.append(m)
     return res
 
 
 def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=None, eval_every: Optional[int] = None,
           eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
-          render_maps: bool = False):
+          render_maps: bool = False, ssim: bool = False):
     """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device.  ``render_maps``: the final
-    test render also writes the depth / opacity maps of every image (``infer(maps=True)``)."""
+    test render also writes the depth / opacity maps of every image (``infer(maps=True)``).  ``ssim``: the periodic evaluation and
+    the final test render also compute each image's SSIM (``evaluate(ssim=True)``; ``metrics_eval.json`` / ``metrics_test.json``)."""
     import json
     from dataclasses import asdict
     device = device or train_rays.rays_o.device
@@ -893,7 +926,7 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
             print(f"step {step}/{n_steps} loss {lv:.5f} occupancy {ov:.3f} samples {int(tr.last['n_samples'])}")
         if eval_every and eval_set is not None and step % eval_every == 0 and step > 0:
             idx = list(range(eval_step, min(eval_step + eval_n, len(eval_set))))
-            eval_metrics.extend(asdict(m) for m in evaluate(eval_set, infer(tr, eval_set, idx, output, f"test_{step}"), idx))
+            eval_metrics.extend(asdict(m) for m in evaluate(eval_set, infer(tr, eval_set, idx, output, f"test_{step}"), idx, ssim=ssim))
             eval_step += eval_n
     test_metrics = None
     if test_set is not None:
@@ -902,7 +935,7 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
         if render_maps:
             rendered = [r["rgb"] for r in rendered]
         if test_set.rgbs:
-            test_metrics = [asdict(m) for m in evaluate(test_set, rendered, idx)]
+            test_metrics = [asdict(m) for m in evaluate(test_set, rendered, idx, ssim=ssim)]
     train_metrics = [{"loss": lv, "occupancy": ov} for lv, ov in log.tolist()]
     if output is not None:
         torch.save(tr.renderer.state_dict(), output / "model.pt")            # run.py:308

@@ -10,7 +10,7 @@ import random
 import uuid
 from pathlib import Path
 
-# (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps and --distortion_weight
+# (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight and --ssim
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -25,6 +25,7 @@ FLAGS = (
     ("--max_steps", dict(type=int, default=None, help="stop early (the recipe's step count is 2048*4096/batch_size)")),
     ("--render_maps", dict(action="store_true", help="the final test render also writes depth / opacity maps")),
     ("--distortion_weight", dict(type=float, default=0.0, help="weight of the Mip-NeRF 360 distortion loss (0: off; 1e-3 .. 1e-2 is usual)")),
+    ("--ssim", dict(action="store_true", help="metrics_eval.json / metrics_test.json also carry each image's SSIM (else 0.0)")),
 )
 
 
@@ -76,7 +77,7 @@ def main(argv=None):
     cfg = TrainConfig(method=args.method, scene_type=args.scene_type, batch_size=args.batch_size, n_samples=args.n_samples, seed=seed,
                       distortion_weight=args.distortion_weight)
     train(cfg, train_rays, load_split(data, root, "val", device, rays=False), load_split(data, root, "test", device, rays=False),
-          run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps)
+          run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim)
 
 
 if __name__ == "__main__":
