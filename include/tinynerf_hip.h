@@ -579,9 +579,41 @@ int tn_ssim(const float *a, const float *b, int64_t H, int64_t W, int32_t C, flo
  * in one launch; rgbs / out_rgb may be NULL. */
 int tn_gather_rays(const float *rays_o, const float *rays_d, const float *rgbs, const int32_t *idx, int64_t n,
                    float *out_o, float *out_d, float *out_rgb, void *stream);
+/* The same draw for a photographed scene, without ray tables: the rays are made from a camera table (one pose, lens and size per
+ * image) and the 8-bit colours.  Every pointer of the table is a DEVICE pointer, the struct itself lives on the host.
+ * Ray i belongs to flat pixel g = first + stride * (idx ? idx[i] : i) of the split (row-major inside an image, images in table
+ * order): a shuffled training block (idx = int32 indices, first = rank, stride = world size for a rank's share), a whole image
+ * (idx = NULL, first = pixel_offset[img], stride = 1).  The image is found by binary search in pixel_offset.
+ *   xd = (u + 0.5 - cx) / fx, yd = (v + 0.5 - cy) / fy                                  (image axes, y down)
+ *   model 0 (pinhole):  (x, y) = (xd, yd)
+ *   model 1 (OpenCV):   (x, y) solves xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2), yd = y rad + 2 p2 x y + p1 (r2 + 2 y^2),
+ *                       rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3 + k4 r2^4, r2 = x^2 + y^2   (Newton from (xd, yd), fixed iteration count)
+ *   model 2 (fisheye):  theta_d = |(xd, yd)|, theta solves theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8);
+ *                       camera direction (xd s, -yd s, -cos theta), s = sin(theta) / theta_d (1 at the centre)
+ *   pinhole / OpenCV camera direction (x, -y, -1): OpenGL camera axes (x right, y up, looking down -z) as the reference's
+ *   data.py:52-70, which model 0 reproduces.
+ * out_d [n,3] = R dir / |R dir| (R = the 3 x 3 of c2w); out_o [n,3] = the translation column, bit for bit; out_rgb [n,3] =
+ * float(byte) / 255, correctly rounded (may be NULL; needs cams->rgb otherwise).  A pixel where the lens model is not invertible and
+ * the iteration ends non-finite gets its pinhole direction: the outputs are always finite and of unit length.  An idx entry that
+ * leads outside the table (not checkable on the host) reads the nearest pixel of the table; nothing is written outside [0, n).
+ * TN_E_SIZE: n < 0, n_img < 1, n_pixels < 1, and -- idx == NULL -- first or first + stride * (n - 1) outside [0, n_pixels);
+ * n == 0 returns TN_OK without a launch.  No reference call site: the reference stubs its nerfstudio loader (data.py:162-167). */
+typedef struct tn_camera_table {
+    const float *c2w;            /* [n_img][12]  rows of the 3 x 4 camera-to-world matrix */
+    const float *lens;           /* [n_img][10]  fx fy cx cy k1 k2 k3 k4 p1 p2 (pixels) */
+    const int32_t *model;        /* [n_img]      0 pinhole, 1 OpenCV radial-tangential, 2 OpenCV fisheye (TN_LENS_*) */
+    const int32_t *size;         /* [n_img][2]   w h */
+    const int64_t *pixel_offset; /* [n_img + 1]  first flat pixel of every image; pixel_offset[n_img] = n_pixels */
+    const uint8_t *rgb;          /* [n_pixels][3] or NULL (pose-only sets) */
+    int64_t n_pixels;            /* host copy of pixel_offset[n_img]: the range checks need it without a device read */
+    int32_t n_img, reserved;
+} tn_camera_table;
+enum { TN_LENS_PINHOLE = 0, TN_LENS_OPENCV = 1, TN_LENS_FISHEYE = 2 };
+int tn_camera_rays(const tn_camera_table *cams, const int32_t *idx, int64_t first, int64_t stride, int64_t n,
+                   float *out_o, float *out_d, float *out_rgb, void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * optimizer step of the harness                        (reference run.py:186,258-260: torch.optim.Adam)
+ * optimizer step of the harness                       (reference run.py:186,258-260: torch.optim.Adam)
  * One pass per parameter tensor: g' = g + wd*p (coupled L2, as torch), m = b1 m + (1-b1) g',
  * v = b2 v + (1-b2) g'^2, p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps); optionally zeroes g for the
  * next step.  28 B/element instead of torch's multi-kernel foreach path. */

@@ -107,6 +107,15 @@ class CobafaDesc(C.Structure):
     ]
 
 
+LENS_PINHOLE, LENS_OPENCV, LENS_FISHEYE = 0, 1, 2      # tn_camera_table.model (TN_LENS_*)
+
+
+class CameraTable(C.Structure):
+    """tn_camera_table: device pointers, the struct itself on the host"""
+    _fields_ = [("c2w", C.c_void_p), ("lens", C.c_void_p), ("model", C.c_void_p), ("size", C.c_void_p), ("pixel_offset", C.c_void_p),
+                ("rgb", C.c_void_p), ("n_pixels", C.c_int64), ("n_img", C.c_int32), ("reserved", C.c_int32)]
+
+
 _lib: Optional[C.CDLL] = None
 _TRACE = bool(os.environ.get("TN_TRACE"))
 

@@ -34,6 +34,7 @@ SOURCES = {
     "sampler.hip": STRICT,
     "planes_reg.hip": FAST,
     "metrics.hip": FAST,
+    "cameras.hip": FAST,
     "kplanes.hip": FAST + ["-munsafe-fp-atomics"],
     "cobafa.hip": STRICT + ["-munsafe-fp-atomics"],   # sawtooth warp x (res-1): an fma in f*x - floor moves taps
     "mlp.hip": FAST,

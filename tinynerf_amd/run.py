@@ -150,10 +150,23 @@ def build_renderer(cfg: TrainConfig, bg_color: Optional[torch.Tensor], device: t
 class Trainer:
     """One object = the body of ``train()`` (run.py:97-319) with ``step()`` as the loop iteration."""
 
-    def __init__(self, cfg: TrainConfig, rays_o: torch.Tensor, rays_d: torch.Tensor, rgbs: torch.Tensor,
-                 bg_color: Optional[torch.Tensor], device: torch.device, rank: int = 0, world_size: int = 1):
+    def __init__(self, cfg: TrainConfig, rays_o: Optional[torch.Tensor], rays_d: Optional[torch.Tensor], rgbs: Optional[torch.Tensor],
+                 bg_color: Optional[torch.Tensor], device: torch.device, rank: int = 0, world_size: int = 1, *, ray_source=None):
+        """``ray_source``: a ``rays.CameraRays`` with colours instead of the three tables (which are then None) -- the candidate rays of
+        every step are made by ``tn_camera_rays`` from its camera table where ``tn_gather_rays`` reads the tables, launch for launch.
+        N > 1: every rank holds the whole source and walks its own share, the flat pixels ``rank + world_size * j``."""
         self.cfg, self.device, self.rank, self.world = cfg, device, rank, world_size
         self.rays_o, self.rays_d, self.rgbs = rays_o, rays_d, rgbs
+        self.ray_source = ray_source
+        if ray_source is not None:
+            if rays_o is not None or rays_d is not None or rgbs is not None:
+                raise ValueError("Trainer: either the ray tables or ray_source, not both")
+            if ray_source.rgb is None:
+                raise ValueError("Trainer: ray_source has no colours to train on")
+            if ray_source.device != torch.device(device) and ray_source.device.index is not None and torch.device(device).index is not None:
+                raise ValueError("Trainer: ray_source lives on another device")
+        # rays this rank walks: its table, or its share of the source
+        self._source_rays = 0 if ray_source is None else len(range(rank, ray_source.n_rays, world_size)) if world_size > 1 else ray_source.n_rays
         with torch.random.fork_rng(devices=[]):         # identical parameters on every rank, the caller's RNG stream untouched
             torch.manual_seed(cfg.seed)
             self.renderer, self.occupancy_grid, self.ray_provider = build_renderer(cfg, bg_color, device)
@@ -241,6 +254,10 @@ class Trainer:
         # whichever stream allocated them while the other stream's kernel is still queued
         self._graveyard: List[torch.Tensor] = []
 
+    @property
+    def n_rays(self) -> int:
+        return self._source_rays if self.ray_source is not None else self.rays_o.size(0)
+
     def __del__(self):
         side = getattr(self, "_side", None)
         if side is not None:             # a side pass may still be writing into buffers this object owns
@@ -283,7 +300,7 @@ class Trainer:
         rays (bench.py: its own views; the tests: ``rays[rank::world]``), so per-rank permutations of per-rank tables are
         disjoint by construction and an epoch of the job visits every ray once.  Deviation: the reference's partial last
         loader batch of an epoch (DataLoader without drop_last) is filled up from the next epoch instead."""
-        n_rays = self.rays_o.size(0)
+        n_rays = self.n_rays
         self._on_stream(self._perm, self._carry)
         while self._carry.numel() + (0 if self._perm is None else self._perm.numel() - self._perm_pos) < m:
             if self._perm is not None:
@@ -323,7 +340,7 @@ class Trainer:
         n_b = n_b or min(4096, max(2, int(self._k_guess * 1.12) + 3))
         R_all = n_b * B
         if cfg.deterministic:
-            idx = ((self._cursor + torch.arange(R_all, device=dev)) % self.rays_o.size(0)).to(torch.int32)
+            idx = ((self._cursor + torch.arange(R_all, device=dev)) % self.n_rays).to(torch.int32)
         else:
             idx = self._epoch_block(R_all)                     # int32
         # origins, directions and target colours of the candidate rays in one launch (three index kernels + an index cast
@@ -332,8 +349,11 @@ class Trainer:
         o = self._buf(f"cand_o{self._info_turn}", (R_all, 3), torch.float32)
         d = self._buf(f"cand_d{self._info_turn}", (R_all, 3), torch.float32)
         rgb = self._buf(f"cand_rgb{self._info_turn}", (R_all, 3), torch.float32)
-        L.call("tn_gather_rays", dev, L.ptr(self.rays_o), L.ptr(self.rays_d), L.ptr(self.rgbs), L.ptr(idx), C.c_int64(R_all), L.ptr(o), L.ptr(d),
-               L.ptr(rgb))
+        if self.ray_source is not None:        # the same draw from the camera table: rays made, not read (rank's share: first = rank, stride = world)
+            self.ray_source.gather(idx, o, d, rgb, first=self.rank if self.world > 1 else 0, stride=self.world if self.world > 1 else 1)
+        else:
+            L.call("tn_gather_rays", dev, L.ptr(self.rays_o), L.ptr(self.rays_d), L.ptr(self.rgbs), L.ptr(idx), C.c_int64(R_all), L.ptr(o), L.ptr(d),
+                   L.ptr(rgb))
         desc = self.ray_provider._desc(dev, not cfg.deterministic, None)
         desc.seed = jitter_seed(cfg.seed, self._batch_no, self.rank)       # (a redrawn block repeats it: same rays, same jitter)
         maskbits = self._buf("maskbits", (R_all, n_chunks), torch.int64)
@@ -372,7 +392,7 @@ class Trainer:
         self._k_guess = k
         self._batch_no += 1
         self.last_plan_seed = int(pend["desc"].seed)      # (the counter RNG's seed of this batch's sampling jitter: the tests read it)
-        self._cursor = (self._cursor + R) % self.rays_o.size(0)
+        self._cursor = (self._cursor + R) % self.n_rays
         if not self.cfg.deterministic:
             self._advance(R)
         info = pend["info"][:R]
@@ -904,15 +924,21 @@ def evaluate(dataset, rendered: List[torch.Tensor], indices: List[int], ssim: bo
 def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=None, eval_every: Optional[int] = None,
           eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
           render_maps: bool = False, ssim: bool = False):
-    """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device.  ``render_maps``: the final
+    """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device, or a data.CameraRaysDataset (a
+    photographed scene: the trainer makes its rays from the camera table, ``Trainer(ray_source=...)``).  ``render_maps``: the final
     test render also writes the depth / opacity maps of every image (``infer(maps=True)``).  ``ssim``: the periodic evaluation and
     the final test render also compute each image's SSIM (``evaluate(ssim=True)``; ``metrics_eval.json`` / ``metrics_test.json``)."""
     import json
     from dataclasses import asdict
-    device = device or train_rays.rays_o.device
+    from .data import CameraRaysDataset
+    on_cameras = isinstance(train_rays, CameraRaysDataset)
+    device = device or (train_rays.device if on_cameras else train_rays.rays_o.device)
     cfg.scene_scale = getattr(train_rays, "scene_scale", cfg.scene_scale)
-    tr = Trainer(cfg, train_rays.rays_o, train_rays.rays_d, train_rays.rgbs,
-                 None if train_rays.bg_color is None else train_rays.bg_color.to(device), device)
+    bg = None if train_rays.bg_color is None else train_rays.bg_color.to(device)
+    if on_cameras:
+        tr = Trainer(cfg, None, None, None, bg, device, ray_source=train_rays.source)
+    else:
+        tr = Trainer(cfg, train_rays.rays_o, train_rays.rays_d, train_rays.rgbs, bg, device)
     n_steps = tr.steps if max_steps is None else min(tr.steps, max_steps)
     eval_metrics, eval_step = [], 0
     # {loss, occupancy} of EVERY step like the reference (run.py:262-266), kept on the device and read back in one copy

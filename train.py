@@ -3,6 +3,8 @@
 
     python train.py --data data/lego --datatype synthetic --output out --method kplanes \\
                     --batch_size 1024 --n_samples 1024 --scene_type aabb
+    python train.py --data captures/garden --datatype nerfstudio --output out --method kplanes \\
+                    --scene_type unbounded --downscale 4
 """
 import argparse
 import os
@@ -10,7 +12,8 @@ import random
 import uuid
 from pathlib import Path
 
-# (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight and --ssim
+# (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight, --ssim,
+# --downscale and --holdout_every
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -26,6 +29,8 @@ FLAGS = (
     ("--render_maps", dict(action="store_true", help="the final test render also writes depth / opacity maps")),
     ("--distortion_weight", dict(type=float, default=0.0, help="weight of the Mip-NeRF 360 distortion loss (0: off; 1e-3 .. 1e-2 is usual)")),
     ("--ssim", dict(action="store_true", help="metrics_eval.json / metrics_test.json also carry each image's SSIM (else 0.0)")),
+    ("--downscale", dict(type=int, default=1, help="nerfstudio: load the images N times smaller (images_N/ if present, else box-filtered)")),
+    ("--holdout_every", dict(type=int, default=8, help="nerfstudio captures without split lists: every N-th frame is val / test")),
 )
 
 
@@ -53,14 +58,29 @@ def load_split(data, root: Path, split: str, device, rays: bool):
     return data.RaysDataset(scene, device) if rays else data.PoseDataset(scene, device)
 
 
+def load_datasets(args, device):
+    """args -> (train rays, eval set, test set); host work only (files, poses, uploads): no kernel runs here.  A synthetic scene becomes
+    ray tables (RaysDataset / PoseDataset), a nerfstudio capture camera tables (CameraRaysDataset / CameraPoseDataset)."""
+    from tinynerf_amd import data
+    root = Path(args.data)
+    if args.datatype == "synthetic":
+        train_rays = load_split(data, root, "train", device, rays=True)
+        if train_rays is None:
+            raise FileNotFoundError(root / "transforms_train.json")
+        return train_rays, load_split(data, root, "val", device, rays=False), load_split(data, root, "test", device, rays=False)
+    if args.datatype == "nerfstudio":
+        def split(name):
+            return data.parse_nerfstudio(root, name, downscale=args.downscale, holdout_every=args.holdout_every)
+        return (data.CameraRaysDataset(split("train"), device), data.CameraPoseDataset(split("val"), device),
+                data.CameraPoseDataset(split("test"), device))
+    raise NotImplementedError(args.datatype)
+
+
 def main(argv=None):
     args = parse_args(argv)
-    if args.datatype != "synthetic":
-        raise NotImplementedError()                     # as in the reference (train.py:30-31)
 
     import numpy as np
     import torch
-    from tinynerf_amd import data
     from tinynerf_amd.run import TrainConfig, train
 
     seed = int(os.environ.get("SEED", 0))
@@ -68,16 +88,12 @@ def main(argv=None):
         for seeder in (torch.manual_seed, np.random.seed, random.seed):
             seeder(seed)
     device = torch.device("cuda")
-    root = Path(args.data)
-    train_rays = load_split(data, root, "train", device, rays=True)
-    if train_rays is None:
-        raise FileNotFoundError(root / "transforms_train.json")
+    train_rays, eval_set, test_set = load_datasets(args, device)
     run_dir = fresh_run_dir(Path(args.output), args)
     print(f"Experiment saved to {run_dir}")
     cfg = TrainConfig(method=args.method, scene_type=args.scene_type, batch_size=args.batch_size, n_samples=args.n_samples, seed=seed,
                       distortion_weight=args.distortion_weight)
-    train(cfg, train_rays, load_split(data, root, "val", device, rays=False), load_split(data, root, "test", device, rays=False),
-          run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim)
+    train(cfg, train_rays, eval_set, test_set, run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim)
 
 
 if __name__ == "__main__":
