@@ -464,6 +464,40 @@ int tn_cobafa_fwd(const tn_cobafa_desc *desc, const float *x, int64_t n, float *
 int tn_cobafa_bwd(const tn_cobafa_desc *desc, const float *x, int64_t n, const float *grad_feat, float *grad_coef,
                   float *const *grad_basis, void *stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Multiresolution hash-grid field (Instant-NGP, Mueller et al. 2022).  No reference call site: the reference has three
+ * fields (Vanilla, K-Planes, Cobafa; run.py:130-152) and no hash encoding.
+ * Level plan, made by the CALLER in float64 and handed over as integers (no kernel computes a resolution): L levels,
+ *   b = exp(ln(N_max / N_min) / (L - 1)) (1 for L = 1), N_l = floor(N_min * b^l + 0.5); level l has N_l + 1 nodes per axis.
+ *   dense  when (N_l + 1)^3 <= T = 2^log2_T: (N_l + 1)^3 entries, rounded up to a multiple of 8 (the padding is never read);
+ *   hashed otherwise: T entries.  offset_l = entries of the levels before l.  One table [sum entries][features], fp32.
+ * Position: x in [-1, 1]^3 = columns 0..2 of a row of `x_stride` floats (7: the packed samples, 3: a plain [n, 3] tensor).
+ *   Per axis in fp32: p = fmaf(x, 0.5f * N_l, 0.5f * N_l) (one rounding), p = min(max(p, 0), N_l) with a NaN landing on 0,
+ *   i = min((int)p, N_l - 1), f = p - i (exact).  Nothing outside the table is ever read, whatever x holds.
+ * Index of node (ix, iy, iz): dense ix + (N_l+1) * (iy + (N_l+1) * iz); hashed (ix ^ iy * 2654435761u ^ iz * 805459861u) & (T - 1)
+ *   in uint32 arithmetic with wrap-around (the primes of Instant-NGP).
+ * Forward:  feat[n, l * F + c] = sum over the 8 corners of w * table[offset_l + idx][c], w = product over the axes of f or 1 - f.
+ * Backward: grad_table[offset_l + idx][c] += w * grad_feat[n, l * F + c] with fp32 atomics (the caller initialises grad_table;
+ *   two corners of one sample that collide in a hashed level both add).  No gradient goes to x.
+ * The tiny-cuda-nn encoding differs (its scale is N_min * b^l - 1 with a +0.5 shift of the position, and b is exp2 of a float):
+ *   its tables do not load here.
+ * TN_E_CONFIG: n_levels outside 1..16, features not 2 or 4, res < 1, a hashed level whose entries is not a power of two, a dense
+ * level with entries < (res + 1)^3, offsets that overlap.  TN_E_SIZE: n < 0 or x_stride < 3.  TN_E_ALIGN: table / grad_table /
+ * feat / grad_feat not 16-byte aligned.  n == 0 returns TN_OK without a launch.
+ * ------------------------------------------------------------------------------------------ */
+#define TN_HASHGRID_MAX_LEVELS 16
+typedef struct tn_hashgrid_desc {
+    int32_t n_levels, features;                  /* features: 2 or 4 */
+    int32_t res[TN_HASHGRID_MAX_LEVELS];         /* N_l */
+    int32_t hashed[TN_HASHGRID_MAX_LEVELS];      /* 0 dense, 1 hashed */
+    int64_t entries[TN_HASHGRID_MAX_LEVELS];     /* dense: padded node count; hashed: a power of two */
+    int64_t offset[TN_HASHGRID_MAX_LEVELS];      /* in entries */
+    const float *table;                          /* [sum entries][features], 16-byte aligned */
+} tn_hashgrid_desc;
+int tn_hashgrid_fwd(const tn_hashgrid_desc *desc, const float *x, int64_t x_stride, int64_t n, float *feat, void *stream);
+int tn_hashgrid_bwd(const tn_hashgrid_desc *desc, const float *x, int64_t x_stride, int64_t n, const float *grad_feat,
+                    float *grad_table, void *stream);
+
 /* north star: "the K-Planes bilinear grid sample ... fused into the same launch" as the persistent MLP.  tn_kplanes_fwd +
  * tn_mlp_fwd_stash_pair in ONE launch (reference call chain core.py:239-249 -> models.py:153-163 -> models.py:70-89): every
  * wave gathers the 3 x 3 planes x 4 taps of its 32 samples straight into the first-layer MFMA operand registers of both

@@ -107,6 +107,19 @@ class CobafaDesc(C.Structure):
     ]
 
 
+TN_HASHGRID_MAX_LEVELS = 16
+
+
+class HashGridDesc(C.Structure):
+    """tn_hashgrid_desc: the level plan of models.hashgrid_levels as integers + the table's device pointer"""
+    _fields_ = [
+        ("n_levels", C.c_int32), ("features", C.c_int32),
+        ("res", C.c_int32 * TN_HASHGRID_MAX_LEVELS), ("hashed", C.c_int32 * TN_HASHGRID_MAX_LEVELS),
+        ("entries", C.c_int64 * TN_HASHGRID_MAX_LEVELS), ("offset", C.c_int64 * TN_HASHGRID_MAX_LEVELS),
+        ("table", C.c_void_p),
+    ]
+
+
 LENS_PINHOLE, LENS_OPENCV, LENS_FISHEYE = 0, 1, 2      # tn_camera_table.model (TN_LENS_*)
 
 

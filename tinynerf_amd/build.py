@@ -37,6 +37,7 @@ SOURCES = {
     "cameras.hip": FAST,
     "kplanes.hip": FAST + ["-munsafe-fp-atomics"],
     "cobafa.hip": STRICT + ["-munsafe-fp-atomics"],   # sawtooth warp x (res-1): an fma in f*x - floor moves taps
+    "hashgrid.hip": FAST + ["-munsafe-fp-atomics"],
     "mlp.hip": FAST,
     "mlp_bwd2.hip": FAST + ["-munsafe-fp-atomics"],
     "mlp_bwd_layers.hip": FAST + ["-munsafe-fp-atomics"],

@@ -777,3 +777,100 @@ class CobafaFeatureField(torch.nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.mlp(self.dropout(self.features(x)))
+
+
+# --------------------------------------------------------------------------------------------
+# Multiresolution hash grid (Instant-NGP, Mueller et al. 2022; no reference counterpart).  Definition: include/tinynerf_hip.h,
+# DESIGN 6e.  One table parameter; all levels' lookups are one launch each way (tn_hashgrid_fwd / _bwd).
+# --------------------------------------------------------------------------------------------
+def hashgrid_levels(n_levels: int, log2_table_size: int, base_resolution: int, max_resolution: int
+                    ) -> Tuple[List[int], List[bool], List[int], List[int]]:
+    """The level plan, on the host in float64: (resolutions N_l, hashed flags, entry counts, offsets in entries).
+    N_l = floor(N_min * b^l + 0.5) with b = exp(ln(N_max / N_min) / (L - 1)); a level whose (N_l + 1)^3 nodes fit into
+    T = 2^log2_table_size entries is dense (node count rounded up to a multiple of 8), the others are hashed into T entries."""
+    import math
+    if not 1 <= n_levels <= L.TN_HASHGRID_MAX_LEVELS:
+        raise ValueError(f"hash grid: n_levels = {n_levels} must be in [1, {L.TN_HASHGRID_MAX_LEVELS}]")
+    if base_resolution < 1 or max_resolution < base_resolution or not 1 <= log2_table_size <= 32:
+        raise ValueError("hash grid: need 1 <= base_resolution <= max_resolution and 1 <= log2_table_size <= 32")
+    b = math.exp(math.log(max_resolution / base_resolution) / (n_levels - 1)) if n_levels > 1 else 1.0
+    T = 1 << log2_table_size
+    res, hashed, entries, offsets = [], [], [], []
+    total = 0
+    for l in range(n_levels):
+        n_l = int(math.floor(base_resolution * b ** l + 0.5))
+        nodes = (n_l + 1) ** 3
+        res.append(n_l)
+        hashed.append(nodes > T)
+        entries.append(T if nodes > T else (nodes + 7) // 8 * 8)
+        offsets.append(total)
+        total += entries[-1]
+    return res, hashed, entries, offsets
+
+
+def _hashgrid_desc(plan, features: int, table: torch.Tensor) -> L.HashGridDesc:
+    res, hashed, entries, offsets = plan
+    d = L.HashGridDesc()
+    d.n_levels, d.features = len(res), features
+    for l in range(len(res)):
+        d.res[l], d.hashed[l], d.entries[l], d.offset[l] = res[l], int(hashed[l]), entries[l], offsets[l]
+    d.table = table.data_ptr()
+    return d
+
+
+class _HashGridFeatures(Function):
+    @staticmethod
+    def forward(ctx: Any, x: torch.Tensor, plan: tuple, accumulate: bool, table: torch.Tensor) -> torch.Tensor:  # type: ignore
+        # accumulate (harness switch, run.Trainer): the scatter adds straight into table.grad where it exists
+        ctx.param_ref = table if accumulate else None
+        lead = x.shape[:-1]
+        x2 = x.reshape(-1, 3).to(torch.float32)
+        if x2.stride(1) != 1 or (x2.size(0) > 1 and x2.stride(0) < 3):
+            x2 = x2.contiguous()
+        if not (x2.is_cuda and table.is_cuda):
+            raise RuntimeError("tinynerf_amd: tensor must be a CUDA (HIP) tensor -- there is no CPU path")
+        if not table.is_contiguous() or table.dtype != torch.float32:
+            raise RuntimeError("tinynerf_amd: the hash grid's table must be a contiguous fp32 tensor")
+        features = table.size(1)
+        n = x2.size(0)
+        stride = x2.stride(0) if n > 1 else 3
+        feat = torch.empty((n, len(plan[0]) * features), device=x2.device)
+        L.call("tn_hashgrid_fwd", x2.device, C.byref(_hashgrid_desc(plan, features, table)), L.ptr(x2), C.c_int64(stride), C.c_int64(n),
+               L.ptr(feat))
+        ctx.save_for_backward(x2, table)
+        ctx.plan = plan
+        return feat.reshape(*lead, feat.size(-1))
+
+    @staticmethod
+    def backward(ctx: Any, grad_feat: torch.Tensor):  # type: ignore
+        x2, table = ctx.saved_tensors
+        n = x2.size(0)
+        stride = x2.stride(0) if n > 1 else 3
+        g = grad_feat.reshape(n, len(ctx.plan[0]) * table.size(1)).to(torch.float32).contiguous()
+        r = ctx.param_ref
+        in_place = (r is not None and r.requires_grad and r.grad is not None and r.grad.is_contiguous() and r.grad.shape == table.shape
+                    and r.grad.dtype == table.dtype)
+        grad = r.grad if in_place else torch.zeros_like(table)
+        L.call("tn_hashgrid_bwd", x2.device, C.byref(_hashgrid_desc(ctx.plan, table.size(1), table)), L.ptr(x2), C.c_int64(stride),
+               C.c_int64(n), L.ptr(g), L.ptr(grad))
+        return (None, None, None, None if in_place else grad)
+
+
+class HashGridFeatureField(torch.nn.Module):
+    """Instant-NGP's multiresolution hash encoding as a feature field: ``n_levels`` grids between ``base_resolution`` and
+    ``max_resolution`` cells per axis, ``features`` floats per node, coarse levels dense and the others hashed into
+    2^``log2_table_size`` entries; one parameter ``table`` [entries of all levels, features], U(-1e-4, 1e-4)."""
+
+    def __init__(self, n_levels: int = 16, features: int = 2, log2_table_size: int = 19, base_resolution: int = 16,
+                 max_resolution: int = 2048):
+        super().__init__()
+        if features not in (2, 4):
+            raise ValueError("hash grid: features must be 2 or 4")
+        self.plan = hashgrid_levels(n_levels, log2_table_size, base_resolution, max_resolution)
+        total = self.plan[3][-1] + self.plan[2][-1]
+        self.table = torch.nn.Parameter(torch.nn.init.uniform_(torch.empty(total, features), -1e-4, 1e-4))
+        self.feature_dim = n_levels * features
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: (..., 3) in [-1, 1] -> (..., n_levels * features), level-major."""
+        return _HashGridFeatures.apply(x, self.plan, bool(self.__dict__.get("accumulate_into_grad")), self.table)

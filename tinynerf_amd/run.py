@@ -27,7 +27,7 @@ from . import _lib as L
 from .core import (ContractionAABB, ContractionMip360, NerfRenderer, OccupancyGrid, RayMarcherAABB,
                    RayMarcherUnbounded, RayProvider, distortion_warp)
 from .optim import FusedAdam
-from .models import (CobafaFeatureField, KPlanesFeatureField, VanillaColorDecoder, VanillaFeatureMLP,
+from .models import (CobafaFeatureField, HashGridFeatureField, KPlanesFeatureField, VanillaColorDecoder, VanillaFeatureMLP,
                      VanillaOpacityDecoder)
 
 
@@ -71,7 +71,7 @@ SIDE_PLAN = _CONFIG.side_plan            # TN_SIDE_PLAN; the next step's sampler
 
 @dataclass
 class TrainConfig:
-    method: str = "kplanes"            # vanilla | kplanes | cobafa   (run.py:130-152)
+    method: str = "kplanes"            # vanilla | kplanes | cobafa   (run.py:130-152) | hashgrid (no reference counterpart: DESIGN 6e)
     scene_type: str = "aabb"           # aabb | unbounded             (run.py:154-162)
     batch_size: int = 1024             # rays per loader batch
     n_samples: int = 1024              # candidates per ray
@@ -100,6 +100,8 @@ class TrainConfig:
     # distortion_weight * mean over the step's rays, in the marcher's normalised ray parameter (core.distortion_warp).  Mip-NeRF 360 and
     # K-Planes use 0.01 and 0.001.  0: the step is the recipe's, launch for launch.  Single GPU only for now.
     distortion_weight: float = 0.0
+    # method "hashgrid": entries per hashed level = 2^this (models.HashGridFeatureField; 19 is Instant-NGP's default, 4 MB per level)
+    hashgrid_log2_table_size: int = 19
 
 
 def jitter_seed(seed: int, batch_no: int, rank: int = 0) -> int:
@@ -126,6 +128,8 @@ def build_renderer(cfg: TrainConfig, bg_color: Optional[torch.Tensor], device: t
         feature_module = CobafaFeatureField(
             basis_res=torch.linspace(32., 128, 6).int().tolist(), coef_res=64,
             freqs=torch.linspace(2., 8., 6).tolist(), channels=[8, 8, 8, 4, 4, 4], mlp_hidden_dim=128)
+    elif cfg.method == "hashgrid":
+        feature_module = HashGridFeatureField(16, 2, cfg.hashgrid_log2_table_size, 16, 2048)
     else:
         raise NotImplementedError(f"Unknown method {cfg.method}.")
     dim = feature_module.feature_dim
@@ -182,6 +186,9 @@ class Trainer:
             raise ValueError(f"TrainConfig.distortion_weight = {cfg.distortion_weight} must be >= 0")
         if cfg.distortion_weight > 0 and world_size > 1:
             raise ValueError("TrainConfig.distortion_weight > 0 is single-GPU for now: the mean over ALL ranks' rays is not exchanged yet")
+        if cfg.method == "hashgrid" and world_size > 1:
+            raise ValueError("TrainConfig.method = 'hashgrid' is single-GPU for now: the table's gradient (49 MB at the default size) "
+                             "has no exchange of its own yet")
         self.renderer.distortion_warp = distortion_warp(self.ray_provider.ray_marcher)
         params = list(self.renderer.parameters())
         for p in params:                                # grads keep the parameter's (channels_last) layout
@@ -198,7 +205,7 @@ class Trainer:
         self.scratch = Arena()
         for i, m in enumerate(mod for mod in self.renderer.feature_module.modules() if isinstance(mod, MLP)):
             m.__dict__["scratch"] = (self.scratch, f"mlp_ws{i}", {}, True, {})      # arena, name, row-view link, -, persistent state
-        if isinstance(self.renderer.feature_module, CobafaFeatureField):
+        if isinstance(self.renderer.feature_module, (CobafaFeatureField, HashGridFeatureField)):
             self.renderer.feature_module.__dict__["accumulate_into_grad"] = True
         self._arena: Dict[str, torch.Tensor] = {}
         self._arena_grown = 0

@@ -18,7 +18,7 @@ FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
     ("--output", dict(type=str, required=True, help="path to the output folder")),
-    ("--method", dict(type=str, required=True, choices=["vanilla", "kplanes", "cobafa"])),
+    ("--method", dict(type=str, required=True, choices=["vanilla", "kplanes", "cobafa", "hashgrid"])),
     ("--scene_type", dict(type=str, default="aabb", choices=["aabb", "unbounded"])),
     ("--batch_size", dict(type=int, default=2048)),
     ("--n_samples", dict(type=int, default=400, help="number of samples per ray")),
