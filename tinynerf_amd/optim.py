@@ -35,73 +35,79 @@ class FusedAdam(torch.optim.Optimizer):
         ``only`` (harness): "reg" = the ``plane_reg`` tensors alone, "rest" = everything else (the trainer may run the planes' pass on a
         stream of its own as soon as their gradients are final, beside the heads' weight-gradient kernels)."""
         loss = closure() if closure is not None else None
-        reg = {}
-        if plane_reg is not None:
-            for slot, (p, H, W, Cc, cy, cx, cl) in enumerate(plane_reg["spec"]):
-                reg[id(p)] = (slot, H, W, Cc, cy, cx, cl)
+        reg = {id(p): (slot, *rest) for slot, (p, *rest) in enumerate(plane_reg["spec"])} if plane_reg is not None else {}
         for group in self.param_groups:
-            b1, b2 = group["betas"]
-            by_step = {}
-            for p in group["params"]:
-                g = p.grad
-                if g is None:
-                    continue
-                if not p.is_cuda:
-                    raise RuntimeError("tinynerf_amd.FusedAdam: parameters must be CUDA (HIP) tensors -- there is no CPU path")
-                if only is not None and (id(p) in reg) != (only == "reg"):
-                    continue
-                st = self.state[p]
-                if not st:
-                    st["step"] = 0
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                m, v = st["exp_avg"], st["exp_avg_sq"]
-                same = g.stride() == p.stride() == m.stride() == v.stride()
-                dense = (p.is_contiguous() or (p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last))
-                         or (p.dim() == 5 and p.is_contiguous(memory_format=torch.channels_last_3d)))
-                if not (same and dense and p.dtype == torch.float32):
-                    raise RuntimeError("tinynerf_amd.FusedAdam: parameter, gradient and state must be dense fp32 with equal strides")
-                # gated tensors share ONE device-side count (they are all skipped or all updated together)
-                by_step.setdefault((st["step"] if (gate is None or id(p) in reg) else -1, p.device, id(p) in reg), []).append((p, g, m, v))
             # one launch per (step count, device): every tensor of the harness shares both
-            for (t, dev, with_reg), tensors in by_step.items():
-                common = (C.c_float(group["lr"]), C.c_float(b1), C.c_float(b2), C.c_float(group["eps"]), C.c_float(group["weight_decay"]),
+            for (t, dev, with_reg), tensors in self._collect(group, reg, gate, only).items():
+                common = (C.c_float(group["lr"]), *map(C.c_float, group["betas"]), C.c_float(group["eps"]), C.c_float(group["weight_decay"]),
                           C.c_int32(t), C.c_int32(1 if self.zero_grad_in_step else 0))
-                if not with_reg:
-                    items = (L.AdamItem * len(tensors))()
-                    for it, (p, g, m, v) in zip(items, tensors):
-                        it.param, it.grad, it.exp_avg, it.exp_avg_sq, it.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-                    if gate is None:
-                        L.call("tn_adam_multi", dev, items, C.c_int32(len(tensors)), *common)
-                    else:
-                        if self._gated_count.get(dev) is None:      # device-side count of the updates that were not gated away
-                            first = min(self.state[p]["step"] for p, _, _, _ in tensors) - 1
-                            # [0]: the count; [1]: raised by the kernel when an updated parameter is not finite (nonfinite_flag)
-                            self._gated_count[dev] = torch.tensor([first, 0], dtype=torch.int32, device=dev)
-                        self._gated_params[dev] = [p for p, _, _, _ in tensors]
-                        L.call("tn_adam_multi_gated", dev, items, C.c_int32(len(tensors)), *common[:5], L.ptr(self._gated_count[dev]),
-                               L.ptr(gate), C.c_int32(common[6].value | 2))
-                    continue
-                items = (L.AdamRegItem * len(tensors))()
-                for it, (p, g, m, v) in zip(items, tensors):
-                    st = self.state[p]
-                    if "shadow" not in st:
-                        st["shadow"] = torch.empty_like(p, memory_format=torch.preserve_format)
-                    slot, H, W, Cc, cy, cx, cl = reg[id(p)]
-                    if (Cc, H, W) != tuple(p.shape[1:]) or not p.is_contiguous(memory_format=torch.channels_last):
-                        raise RuntimeError("tinynerf_amd.FusedAdam: plane_reg expects channels_last [1,C,H,W] planes")
-                    it.param, it.param_out, it.grad = p.data_ptr(), st["shadow"].data_ptr(), g.data_ptr()
-                    it.exp_avg, it.exp_avg_sq, it.n = m.data_ptr(), v.data_ptr(), p.numel()
-                    it.H, it.W, it.C, it.sum_slot, it.cy, it.cx, it.cl1 = H, W, Cc, slot, cy, cx, cl
-                    it.row0, it.row1 = (plane_reg.get("rows") or {}).get(id(p), (0, 0))       # sharded pass: this rank's rows only
-                sums = plane_reg.get("sums")
-                L.call("tn_adam_reg_multi", dev, items, C.c_int32(len(tensors)), *common, C.c_float(plane_reg["upstream"]), L.ptr(sums))
-                for p, _, _, _ in tensors:                   # the updated values live in the second buffer: swap
-                    st = self.state[p]
-                    new, st["shadow"] = st["shadow"], p.data
-                    p.data = new
+                if with_reg:
+                    self._launch_reg(dev, tensors, common, reg, plane_reg)
+                else:
+                    self._launch_plain(dev, tensors, common, gate)
         return loss
+
+    def _state(self, p, shadow: bool = False):
+        """the Adam state of `p`, created at its first use (`shadow`: with the double buffer of the regularised pass)"""
+        st = self.state[p]
+        if "exp_avg" not in st:
+            st.setdefault("step", 0)
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        if shadow and "shadow" not in st:
+            st["shadow"] = torch.empty_like(p, memory_format=torch.preserve_format)
+        return st
+
+    def _collect(self, group, reg, gate, only):
+        """{(step count, device, regularised): [(p, grad, exp_avg, exp_avg_sq)]}: the group's tensors with a gradient, validated, steps advanced"""
+        by_step = {}
+        for p in group["params"]:
+            g = p.grad
+            if g is None:
+                continue
+            if not p.is_cuda:
+                raise RuntimeError("tinynerf_amd.FusedAdam: parameters must be CUDA (HIP) tensors -- there is no CPU path")
+            if only is not None and (id(p) in reg) != (only == "reg"):
+                continue
+            st = self._state(p)
+            st["step"] += 1
+            m, v = st["exp_avg"], st["exp_avg_sq"]
+            same = g.stride() == p.stride() == m.stride() == v.stride()
+            dense = (p.is_contiguous() or (p.dim() == 4 and p.is_contiguous(memory_format=torch.channels_last))
+                     or (p.dim() == 5 and p.is_contiguous(memory_format=torch.channels_last_3d)))
+            if not (same and dense and p.dtype == torch.float32):
+                raise RuntimeError("tinynerf_amd.FusedAdam: parameter, gradient and state must be dense fp32 with equal strides")
+            # gated tensors share ONE device-side count (they are all skipped or all updated together)
+            by_step.setdefault((st["step"] if (gate is None or id(p) in reg) else -1, p.device, id(p) in reg), []).append((p, g, m, v))
+        return by_step
+
+    def _launch_plain(self, dev, tensors, common, gate):
+        items = (L.AdamItem * len(tensors))()
+        for it, (p, g, m, v) in zip(items, tensors):
+            it.param, it.grad, it.exp_avg, it.exp_avg_sq, it.n = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+        if gate is None:
+            return L.call("tn_adam_multi", dev, items, C.c_int32(len(tensors)), *common)
+        if self._gated_count.get(dev) is None:      # device-side count of the updates that were not gated away
+            # [0]: the count; [1]: raised by the kernel when an updated parameter is not finite (nonfinite_flag)
+            self._gated_count[dev] = torch.tensor([min(self.state[p]["step"] for p, _, _, _ in tensors) - 1, 0], dtype=torch.int32, device=dev)
+        self._gated_params[dev] = [p for p, _, _, _ in tensors]
+        L.call("tn_adam_multi_gated", dev, items, C.c_int32(len(tensors)), *common[:5], L.ptr(self._gated_count[dev]),
+               L.ptr(gate), C.c_int32(common[6].value | 2))
+
+    def _launch_reg(self, dev, tensors, common, reg, plane_reg):
+        items = (L.AdamRegItem * len(tensors))()
+        for it, (p, g, m, v) in zip(items, tensors):
+            slot, H, W, Cc, cy, cx, cl = reg[id(p)]
+            if (Cc, H, W) != tuple(p.shape[1:]) or not p.is_contiguous(memory_format=torch.channels_last):
+                raise RuntimeError("tinynerf_amd.FusedAdam: plane_reg expects channels_last [1,C,H,W] planes")
+            it.param, it.param_out, it.grad = p.data_ptr(), self._state(p, shadow=True)["shadow"].data_ptr(), g.data_ptr()
+            it.exp_avg, it.exp_avg_sq, it.n = m.data_ptr(), v.data_ptr(), p.numel()
+            it.H, it.W, it.C, it.sum_slot, it.cy, it.cx, it.cl1 = H, W, Cc, slot, cy, cx, cl
+            it.row0, it.row1 = (plane_reg.get("rows") or {}).get(id(p), (0, 0))       # sharded pass: this rank's rows only
+        L.call("tn_adam_reg_multi", dev, items, C.c_int32(len(tensors)), *common, C.c_float(plane_reg["upstream"]), L.ptr(plane_reg.get("sums")))
+        for p, _, _, _ in tensors:                   # the updated values live in the second buffer: swap
+            st = self.state[p]
+            p.data, st["shadow"] = st["shadow"], p.data
 
     def sync_step_counts(self) -> None:
         """Gated mode keeps the real update count on the device (a skipped "Empty iteration" must not advance the bias
@@ -131,13 +137,7 @@ class FusedAdam(torch.optim.Optimizer):
         """create the Adam moments (and, `shadow`, the double buffer of the regularised pass) of `params` now, on the current stream,
         instead of at their first step -- which the harness may run on a side stream (run.Trainer, TN_ADAM_OVERLAP)"""
         for p in params:
-            st = self.state[p]
-            if "exp_avg" not in st:
-                st.setdefault("step", 0)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            if shadow and "shadow" not in st:
-                st["shadow"] = torch.empty_like(p, memory_format=torch.preserve_format)
+            self._state(p, shadow)
 
     def state_dict(self):
         if self.partial_state_reason:
