@@ -66,6 +66,7 @@ int tn_weights_bwd(const float *sigmas, const float *steps, const int32_t *info,
  * a18  per-ray compositing                                     (reference core.py:256-265)
  * rendered[r] = sum_k w_k rgb_k (+ bg*(1-sum_k w_k) if bg != NULL); opacity[r] optional.
  * bwd: grad_rgbs[k] = w_k*g[r];  grad_weights[k] = <rgb_k, g[r]> - <bg, g[r]>.
+ * One wave per ray; info must be 8-byte aligned (TN_E_ALIGN otherwise), as for the weights entry points.
  * ------------------------------------------------------------------------------------------ */
 int tn_composite_fwd(const float *rgbs, const float *weights, const int32_t *info, const float *bg,
                      float *rendered, float *opacity, int64_t n_samples, int64_t n_rays, void *stream);

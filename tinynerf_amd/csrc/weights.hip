@@ -617,6 +617,7 @@ extern "C" int tn_composite_fwd(const float *rgbs, const float *weights, const i
     TN_REQUIRE(n_samples >= 0 && n_rays >= 0, TN_E_SIZE, "tn_composite_fwd: negative size");
     if (n_rays == 0) return TN_OK;
     TN_REQUIRE(info && rendered && (n_samples == 0 || (rgbs && weights)), TN_E_NULL, "tn_composite_fwd: null pointer");
+    TN_REQUIRE(((uintptr_t)info & 7) == 0, TN_E_ALIGN, "tn_composite_fwd: info must be 8-byte aligned");
     hipLaunchKernelGGL(composite_fwd_kernel, dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream,
                        rgbs, weights, info, bg, rendered, opacity, n_rays);
     return tn::check_launch("composite_fwd_kernel");
@@ -629,6 +630,7 @@ extern "C" int tn_composite_bwd(const float *rgbs, const float *weights, const i
     TN_REQUIRE(n_samples >= 0 && n_rays >= 0, TN_E_SIZE, "tn_composite_bwd: negative size");
     if (n_rays == 0 || n_samples == 0) return TN_OK;
     TN_REQUIRE(rgbs && weights && info && grad_rendered, TN_E_NULL, "tn_composite_bwd: null pointer");
+    TN_REQUIRE(((uintptr_t)info & 7) == 0, TN_E_ALIGN, "tn_composite_bwd: info must be 8-byte aligned");
     hipLaunchKernelGGL(composite_bwd_kernel, dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream,
                        rgbs, weights, info, bg, grad_rendered, grad_rgbs, grad_weights, n_rays);
     return tn::check_launch("composite_bwd_kernel");
