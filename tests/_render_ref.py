@@ -17,35 +17,35 @@ Bounds.  u = 2^-24.  E = EXPF_ULPS bounds the device expf in ulps; one alpha a_j
 error eps_j = (p_j + 2 E) u: the product's rounding moves the exponent by p u, and E ulps are at most 2 E u of the value.
 
   r_T(m), the fp32 multiplications on the path of T_m (m = 64 c + l: chunk c, lane l):
-    7 per finished chunk: wave_scan_mul's six steps on lane 63 (weights.hip:24-27) and the carry update `carry * __shfl(incl, 63)`
-    (:71; in the backward `T *= __shfl(pt, 63)`, :159 / :181);
-    inside the chunk, for l > 0, the scan steps o <= l - 1 that lane l - 1 takes part in, bit_length(l - 1) of them (:26), and
-    `carry * excl` (:66).  Lane 0 multiplies the carry by 1.
-    The backward's T_{k+1} is `T * pt` of the INCLUSIVE scan of lane l (:157 / :179): 7 c + bit_length(l) + 1, which is r_T(k + 1).
+    7 per finished chunk: wave_scan_mul's six steps on lane 63 (wave_scan, weights.hip:56-59) and the carry update `carry * wave_last(incl)`
+    (:148; in the backward `T *= wave_last(pt)`, :209, both paths);
+    inside the chunk, for l > 0, the scan steps o <= l - 1 that lane l - 1 takes part in, bit_length(l - 1) of them (:58), and
+    `carry * wave_excl(incl)` (:143).  Lane 0 multiplies the carry by 1.
+    The backward's T_{k+1} is `T * pt` of the INCLUSIVE scan of lane l (:207): 7 c + bit_length(l) + 1, which is r_T(k + 1).
   forward   |w - w_ref| <= T_ref a_ref eps_k + w_ref (sum_{j<k} eps_j + r_T(k) u + u): alpha's own error acts on 1 - a through T a; T
-            carries the alphas before it and its multiplications; the fp64 product T (1 - a) is rounded to fp32 once (:70).
+            carries the alphas before it and its multiplications; the fp64 product T (1 - a) is rounded to fp32 once (:147).
             w is exactly 0 where w_ref is.  The same sum bounds T itself: |T - T_ref| <= T_ref (sum_{j<k} eps_j + r_T(k) u), and a ray
             on which some T_ref,k lies that close to the threshold is a "danger ray" -- the fixtures hold none (danger_rays).
   backward  |gs - gs_ref| <= step_k u [c_add(count) A_ray + (sum_{j<=k} eps_j / u + r_T(k + 1) + 3) T_{k+1} |g_k|],
-            A_ray = sum_j |w_j g_j|.  The 3: the product with g, the final addition and the product with the step (:157 / :179).
+            A_ray = sum_j |w_j g_j|.  The 3: the product with g, the final addition and the product with the step (:207).
             c_add, the fp32 operations on the path of one term through -total + prefix, nch = ceil(count / 64):
-              register path (count <= 1024): the product w g (:144) 1; the lane's partial sum (:147; its 16 - nch other additions add an
-              exact 0) nch; wave_sum (tn_common.h:38) 6; wave_scan_add (:32-35) 6; `acc += __shfl(ps, 63)` (:158) nch; `acc + ps`,
-              the final addition and the product with the step (:157) 3: 2 nch + 16, nch <= 16;
-              streaming path: the product and the lane's partial sum (:164) 1 + nch; wave_sum 6; wave_scan_add 6; the carry (:180) nch;
-              :179 3: 2 nch + 16 with nch unbounded.
-  composite (m + r) u sum|terms|.  A lane sums nch products (:200; :80 in the fused form) and wave_sum adds 6 levels (:204): the opacity
+              register path (count <= 1024): the product w g (:200) 1; the lane's partial sum (:219; its 16 - nch other additions add an
+              exact 0) nch; wave_sum (tn_common.h:38) 6; wave_scan_add (:56-59) 6; `acc += wave_last(ps)` (:208) nch; `acc + ps`,
+              the final addition and the product with the step (:207) 3: 2 nch + 16, nch <= 16;
+              streaming path: the product and the lane's partial sum (:226) 1 + nch; wave_sum 6; wave_scan_add 6; the carry (:208) nch;
+              :207 3: 2 nch + 16 with nch unbounded.
+  composite (m + r) u sum|terms|.  A lane sums nch products (Composite::add, :82, in both forms) and wave_sum adds 6 levels (:90): the opacity
             has m = nch + 6, r = 0; a colour without bg m = nch + 6 and r = 1 (the product); with bg the longest path is a weight's
-            through the opacity (nch + 6), `1 - o`, the product with bg and the final addition (:206): m = nch + 7, r = 2, and
-            sum|terms| holds |bg| (1 + sum |w|).  grad_w: three products, two additions, the subtraction of gbg (:229-230): m = 3,
-            r = 1 on sum_c |rgb_c g_c| + sum_c |bg_c g_c|; tn_render_rays_bwd_dw's extra is one more addition (:126): m = 4 and
+            through the opacity (nch + 6), `1 - o`, the product with bg and the final addition (:92): m = nch + 7, r = 2, and
+            sum|terms| holds |bg| (1 + sum |w|).  grad_w: three products, two additions, the subtraction of gbg (:113-114): m = 3,
+            r = 1 on sum_c |rgb_c g_c| + sum_c |bg_c g_c|; tn_render_rays_bwd_dw's extra is one more addition (:188): m = 4 and
             |extra| joins the terms.
   fused     tn_render_rays_fwd composites with its own weights: those are held to the forward bound, and `rendered` to the composite
             of the weights the launch wrote, with the composite's bound.  tn_render_rays_bwd(_dw) feeds grad_w to the backward unrounded by any store: with G_j = sum|terms| of
             grad_w_j and r_g = m + r of it (4, or 5 with extra), the backward bound holds with |g| -> G, A_ray = sum_j |w_j| G_j,
             c_add + r_g and 3 + r_g.
-  sumsq     a thread adds its m = ceil(n / (blocks 256)) squares with fmaf in fp32 (:246), blocks = min(ceil(n / 256), 512) (:645);
-            d = fl(r - t) is squared: r = 2.  Lanes, waves and blocks are added in fp64 (:248-254): 2^-50 (sum + |start|) on top.
+  sumsq     a thread adds its m = ceil(n / (blocks 256)) squares with fmaf in fp32 (:281), blocks = min(ceil(n / 256), 512) (:578);
+            d = fl(r - t) is squared: r = 2.  Lanes, waves and blocks are added in fp64 (:283-289): 2^-50 (sum + |start|) on top.
 
 EXPF_ULPS = 1.  Unverified: OCML is believed to document 1 ulp for the fp32 exp.  The constant is NOT tuned on the multi-sample
 fixtures.  Every fixture stayed inside its bounds on an MI355X with E = 1 (the table in tests/test_hip_render.py), so it did not move

@@ -9,21 +9,22 @@ that each of eleven mutants of it does not.
   tn_weights_bwd              every fixture, w = the reference weights rounded to fp32
   tn_composite_fwd / _bwd     exact kind bit for bit (opacity included), general kind inside the bound, NaN colours at masked samples,
                               grad_rgbs / grad_weights NULL in turn
-  tn_render_rays_fwd/_bwd/_dw against the yardstick directly (the equal-to-two-launches tests stay in test_hip_core / _distortion)
+  tn_render_rays_fwd/_bwd/_dw against the yardstick directly; the forward also bit for bit against tn_composite_fwd on the weights it wrote
+                              and tn_weights_fwd (the other equal-to-two-launches tests stay in test_hip_core / _distortion)
   tn_mse_grad / _gated        n in {1, 3, 255, 256, 257, 768, 131072, 131073}: grad bit for bit, sumsq inside its bound on top of a
                               non-zero start, scale_dev NULL and set, the gate at 1, 0, -1 and NaN
 
-Largest err / bound per kernel, measured on an MI355X with EXPF_ULPS = 1 (each test prints its own figure, the module prints the
-maxima at its end).  The figures are of a run before the `singles` fixture existed, before `unbounded` had a wall on every ray of
-its second ladder, and with tn_render_rays_fwd's `rendered` held to the reference weights' composite plus the carried weight bound;
-they have not been measured again since:
-  tn_weights_fwd / _gate   0.755        tn_render_rays_fwd      0.452
-  tn_weights_bwd           0.120        tn_render_rays_bwd      0.099
-  tn_composite_fwd         0.293        tn_render_rays_bwd_dw   0.123
-  tn_composite_bwd         0.498        tn_mse_grad(_gated)     0.091 (sumsq; grad bit for bit)
-The exact composite kind, grad_rgbs and the MSE gradient matched bit for bit.  On the one single-sample ray with alpha >= 1/2 that
-run held, no excess of expf over the rounding of w was seen (0.04 ulp left beyond it); EXPF_ULPS stayed at 1 because every fixture
-passed with it, not because of that figure.
+Largest err / bound per kernel, measured on an MI355X with EXPF_ULPS = 1 on the fixtures as they stand (each test prints its own
+figure, the module prints the maxima at its end; LABNOTES 9.8 is the record of the run, in which the parent commit's library gave
+the same figures in every row):
+  tn_weights_fwd / _gate   0.755        tn_render_rays_fwd      0.496
+  tn_weights_bwd           0.211        tn_render_rays_bwd      0.134
+  tn_composite_fwd         0.293        tn_render_rays_bwd_dw   0.124
+  tn_composite_bwd         0.573        tn_mse_grad(_gated)     0.091 (sumsq; grad bit for bit)
+The exact composite kind, grad_rgbs and the MSE gradient matched bit for bit, and so did tn_render_rays_fwd with its two halves
+(tn_composite_fwd on the weights it wrote, tn_weights_fwd on its inputs) on every fixture.  On the `singles` fixture expf's largest
+error lay between 0.55 and 0.86 ulp (beyond the rounding of w, and with it); EXPF_ULPS stayed at 1 because every fixture passed
+with it, not because of that figure.
 """
 import ctypes as C
 
@@ -201,6 +202,12 @@ def test_render_rays_against_fp64(name, with_bg):
     worst = _note("tn_render_rays_fwd", max(worst, ref.worst_ratio(got_out, rout, bound, f"{name} tn_render_rays_fwd rendered")))
     if not fx["info"][:, 1].any():                          # no samples at all: the background, or nothing
         ref.same_bits(got_out, np.broadcast_to(ref.BG if with_bg else np.zeros(3, f32), (R, 3)), f"{name} all-empty rendered")
+    # the fused launch is its two halves bit for bit: tn_composite_fwd on the weights it wrote, tn_weights_fwd on its inputs
+    out2, w2 = _buf(R, 3), _buf(n)
+    _call("tn_composite_fwd", _ptr(d_rgb), _ptr(w), _ptr(x.info), _ptr(d_bg), _ptr(out2), C.c_void_p(None), *_sizes(fx))
+    _call("tn_weights_fwd", _ptr(x.sig), _ptr(x.step), _ptr(x.info), C.c_float(thr), _ptr(w2), *_sizes(fx))
+    ref.same_bits(_np(out2, R), got_out, f"{name} tn_composite_fwd on tn_render_rays_fwd's weights, rendered")
+    ref.same_bits(_np(w2, n), got_w, f"{name} tn_weights_fwd against tn_render_rays_fwd, weights")
     # backward, on the reference weights
     d_w = _dev(w32)
     res = {}
