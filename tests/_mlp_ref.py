@@ -316,6 +316,7 @@ PART_A = {
     "mlp36_128x1_128":   (Spec("none", 36, 0, 128, 0, 128, "none"), "matmul"),
     "mlp36_128x2_128":   (Spec("none", 36, 0, 128, 1, 128, "none"), "matmul"),      # Cobafa's input width
     "mlp36_128x2_40":    (Spec("none", 36, 0, 128, 1, 40, "none"), "matmul"),       # output below H, not a multiple of 32
+    "mlp36_128x2_37":    (Spec("none", 36, 0, 128, 1, 37, "none"), "matmul"),       # output below H, odd: the scalar y stores, a second block with 5 rows
     "mlp147_128x2_288":  (Spec("none", 147, 0, 128, 1, 288, "none"), "matmul"),     # output wider than H
     "pe60_128x2_128":    (Spec("posenc", 3, 10, 128, 1, 128, "none"), "matmul"),
     "color59_128x2_3":   (Spec("dircat", 32, 4, 128, 1, 3, "sigmoid"), "matmul"),    # VanillaColorDecoder(4, 32, 128, 1)

@@ -13,12 +13,13 @@ B. Production-depth stacks (the bound rejects every sample there) with SPARSE up
 Sizes.  1, 31, 32, 33, 65 and the smallest n at which a persistent loop runs a second round: 8193 at every width, plus 16385 at widths 128
 and 256.  Which launches that reaches, read off their grid computations (32-sample tiles, at most 256 x per_cu workgroups):
 * 8193 (tile 256 = sample 8192 opens the second round): the weight-gradient launches with one tile per workgroup and round on 256
-  workgroups -- fp32 mode at width 128 / 256: ``min(n_tiles, 256)`` in launch_wgrad_lds (mlp_bwd_layers.hip); width 64: ``grid_blocks(n, 1,
-  256)`` for mlp_wgrad4_kernel (mlp_bwd2.hip, grid_blocks in mlp_stage.h) -- and the width-256 layer forward / data-gradient kernels,
-  ``min(ceil(n_tiles / STREAMS), 256)`` workgroups with STREAMS = 1 (launch_* in mlp_bwd_layers.hip / mlp_f2_layers.hip / mlp_b3_layers.hip).
-* 16385 (sample 16384): the f16x2 and bf16x3 weight-gradient launches, ``min(n_tiles, 256 * per_cu)`` with per_cu = 2 at both widths
-  (mlp_f2_layers.hip / mlp_b3_layers.hip launch_wgrad: 48 / 72 KB of LDS, two workgroups per CU), and the width-128 layer forward / data-
-  gradient kernels (STREAMS = 2).
+  workgroups -- fp32 mode at width 128 / 256: ``grid_blocks(n, 1, 256)`` = min(n_tiles, 256) in launch_wgrad_lds (mlp_bwd_layers.hip);
+  width 64: ``grid_blocks(n, 1, 256)`` for mlp_wgrad4_kernel (mlp_bwd2.hip, grid_blocks in mlp_stage.h) -- and the width-256 layer forward /
+  data-gradient kernels, ``stream_blocks(n, STREAMS)`` = min(ceil(n_tiles / STREAMS), 256) workgroups (mlp_layers.h) with STREAMS = 1
+  (launch_*_wreg in mlp_bwd_layers.hip, launch_*_f2 in mlp_f2_layers.hip, launch_*_b3 in mlp_b3_layers.hip).
+* 16385 (sample 16384): the f16x2 and bf16x3 weight-gradient launches, ``grid_blocks(n, 1, 256 * per_cu)`` = min(n_tiles, 256 * per_cu)
+  with per_cu = 2 at both widths (launch_wgrad_f2 / launch_wgrad_b3: 48 / 72 KB of LDS, two workgroups per CU), and the width-128 layer
+  forward / data-gradient kernels (STREAMS = 2).
 * NOT reached by any n of part A: the cross-layer launches of mlp_fused_f2.hip (the default f16x2 form) run ``min(ceil(n_tiles / NW),
   256)`` workgroups with NW = 4 or 8 waves, so their second round opens at sample 32768 or 65536; part B's 40037 gives the NW = 4 launches
   a second round (its probes 40004 and 40036 lie in it), the NW = 8 launches (width-128 chain and inference) run one round at every n here.
@@ -34,7 +35,9 @@ Observed on an MI355X (reported, not a tolerance; pytest -s prints every figure)
 over all shapes, sizes, stash on / off and both forms -- width 64: f16x2 y 0.002, grad_x 0.010, dW 0.032, db 0.053; fp32 0.003, 0.013,
 0.046, 0.106.  Width 128: f16x2 0.010, 0.004, 0.078, 0.036; bf16x3 0.011, 0.004, 0.097, 0.041; fp32 0.011, 0.004, 0.061, 0.043.  Width
 256: f16x2 0.004, < 0.001, 0.039, 0.029; bf16x3 0.004, < 0.001, 0.044, 0.029; fp32 0.005, < 0.001, 0.032, 0.023.  Pair forward: 0.003.
-The layer-wise and the cross-layer forms, and stash on and off, give the same figures to three digits.
+The layer-wise and the cross-layer forms, and stash on and off, give the same figures to three digits.  mlp36_128x2_37 (an output below the
+width that is no multiple of 4: the element-wise y stores of the last layer's narrow epilogue, emit_last_narrow in mlp_layers.h, and a second
+output block with five rows) stays below them: y 0.001, grad_x 0.003, dW 0.046, db 0.041 over the three modes.
 """
 import ctypes as C
 

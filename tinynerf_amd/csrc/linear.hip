@@ -19,11 +19,10 @@ namespace {
 
 using tn::f32x16;
 using tn::f32x4;
+using tn::frow;
 
 constexpr int LIN_WAVES = 4;
 constexpr int LIN_MAX = 128;       // weights + four 32-sample tiles in LDS: (128 + 128) x 129 floats = 132 KB
-
-__device__ __forceinline__ int frow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // y [n][N] = x [n][K] A^T (+ bias [N]);  A[i][k] = TRANS ? W[k * ldw + i] : W[i * ldw + k]
 template <bool TRANS>

@@ -40,10 +40,6 @@ using tn::b3::u32x4;
 using tn::f32x16;
 using tn::f32x4;
 
-__device__ __forceinline__ void glds16(const float *src, float *dst) {
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-}
-
 template <int H> struct B3Geom {
     static constexpr int T = H / 32;                // 32-row blocks of the layer's input and of its output
 #ifndef TN_B3_BPW256
@@ -67,33 +63,6 @@ template <int H> struct B3Geom {
     static constexpr size_t lds_bytes = (size_t)STREAMS * STREAM_B + H * 4;
 };
 
-// weights of output rows 32 ob + i as A operands: step s, lane (i, h): W[row][16 s + 8 h + 0..7]
-template <int KS>
-__device__ __forceinline__ void load_weights_rows(const float *__restrict__ W, int ldw, int row, bool ok, int h, Op (&A)[KS]) {
-    const float *wr = W + (int64_t)(ok ? row : 0) * ldw + 8 * h;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wr + 16 * s), w1 = *reinterpret_cast<const f32x4 *>(wr + 16 * s + 4);
-        float v[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-        if (!ok) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) v[e] = 0.0f;
-        }
-        A[s] = tn::b3::split8(v);
-    }
-}
-// ... of W^T: A[i = column 32 kb + i][k = row n]: step s, lane (i, h): W[16 s + 8 h + e][col]
-template <int KS>
-__device__ __forceinline__ void load_weights_cols(const float *__restrict__ W, int ldw, int col, int h, Op (&A)[KS]) {
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        float v[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = W[(int64_t)(16 * s + 8 * h + e) * ldw + col];
-        A[s] = tn::b3::split8(v);
-    }
-}
-
 // B operand of step s for sample j: three ds_read_b128
 template <int SB>
 __device__ __forceinline__ Op read_b(const unsigned short *tile, int j, int h, int s) {
@@ -104,15 +73,6 @@ __device__ __forceinline__ Op read_b(const unsigned short *tile, int j, int h, i
     o.mid = *reinterpret_cast<const u32x4 *>(p + PLANE);
     o.lo = *reinterpret_cast<const u32x4 *>(p + 2 * PLANE);
     return o;
-}
-
-// LDS-direct request of `nrows` (multiple of 8) rows of a tile, starting at row r0 of `rows` ([row][32 samples]) -> stage
-// (lane-linear: one instruction = 8 rows x 128 B = 1 KB)
-template <int NROWS>
-__device__ __forceinline__ void request_rows(const float *rows, int r0, float *stage, int lane) {
-    const float *src = rows + r0 * 32 + 4 * lane;            // 16 B per lane
-#pragma unroll
-    for (int e = 0; e < NROWS / 8; ++e) glds16(src + e * 256, stage + e * 256);
 }
 
 // value pair p (0 .. 8 BPW - 1) of the wave's staged rows -> the three bf16 planes of a tile buffer.  The wave's 32 BPW rows x 32
@@ -134,27 +94,20 @@ __device__ __forceinline__ void convert_pair(const float *sp, unsigned short *np
 // Everything of one tile stream that forward and data gradient share: geometry, prologue, the k loop with the conversion of the
 // next tile and the request of the one after it in the middle, the counted wait + barrier.
 template <int H>
-struct Stream {
+struct Stream : TileWalk<B3Geom<H>::STREAMS, B3Geom<H>::WPS> {       // (wib: the wave owns blocks BPW wib .. + BPW - 1)
     using G = B3Geom<H>;
+    using Walk = TileWalk<G::STREAMS, G::WPS>;
+    using Walk::lane; using Walk::j; using Walk::h; using Walk::stream; using Walk::wib; using Walk::tile_of;
     static constexpr int KS = G::KS, SB = G::SB, PLANE = G::PLANE, BPW = G::BPW;
-    int lane, j, h, wave, stream, wib;          // wib: wave in stream; it owns blocks BPW wib .. + BPW - 1
     unsigned short *tiles;
     float *stage;                               // this wave's 32 BPW rows of the staging area
-    int64_t n_tiles, stride, first, iters;
 
     __device__ __forceinline__ void init(unsigned char *lds_raw, int64_t n) {
-        lane = tn::lane_id(); j = lane & 31; h = lane >> 5;
-        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        stream = wave / G::WPS; wib = wave % G::WPS;
+        Walk::init(n);
         unsigned char *sbase = lds_raw + stream * G::STREAM_B;
         tiles = reinterpret_cast<unsigned short *>(sbase);
         stage = reinterpret_cast<float *>(sbase + 2 * G::TILE_B) + (32 * BPW * wib) * 32;
-        n_tiles = (n + 31) >> 5;
-        stride = (int64_t)gridDim.x * G::STREAMS;
-        first = (int64_t)blockIdx.x * G::STREAMS;
-        iters = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
     }
-    __device__ __forceinline__ int64_t tile_of(int64_t it) const { const int64_t t = first + stream + it * stride; return t < n_tiles ? t : n_tiles - 1; }
     __device__ __forceinline__ const float *sp() const { return stage + (16 * h) * 32 + j; }
     __device__ __forceinline__ unsigned short *np(int buf) const { return tiles + buf * (3 * PLANE) + j * SB + 32 * BPW * wib + 16 * h; }
     __device__ __forceinline__ void request(const float *stash, int64_t tile, int rows_total, int off) const {
@@ -282,7 +235,7 @@ __global__ __launch_bounds__(B3Geom<H>::THREADS) void fwd_b3_kernel(FwdLayerArgs
 #pragma unroll
     for (int bq = 0; bq < BPW; ++bq) {
         const int row = 32 * (BPW * st.wib + bq) + j;
-        load_weights_rows<KS>(a.W, a.K, row, row < a.N, h, A[bq]);
+        read_weight_rows<KS>(a.W, a.K, row, row < a.N, h, [&](int s, const float (&v)[8]) { A[bq][s] = tn::b3::split8(v); });
     }
     st.prologue(stash, a.rows_total, a.off_in);
     int cur = 0;
@@ -305,47 +258,8 @@ __global__ __launch_bounds__(B3Geom<H>::THREADS) void fwd_b3_kernel(FwdLayerArgs
             if constexpr (!LAST) {
                 acc[bq] = tn::relu16(acc[bq]);
                 if (!(TN_B3_ABLATE & 4) || acc[bq][0] == 123.f) wreg_store_block(urow(stash, tile * a.rows_total + a.off_out), ob, j, h, acc[bq]);
-            } else if (a.N == H) {
-                // full-width output (the feature stacks: y = 256 / 128 features): pre-activation rows through the SGPR-base stores,
-                // y as four 16-byte stores per block -- a fixed number of vector-memory operations behind the k loop's request,
-                // so that the tile ends with a counted wait instead of draining them
-                const int64_t row = tile * 32 + j;
-                const bool valid = row < n;
-                f32x16 pre;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) pre[r] = valid ? acc[bq][r] : 0.0f;
-                wreg_store_block(urow(stash, tile * a.rows_total + a.off_out), ob, j, h, pre);
-                float *yr = y + (valid ? row : 0) * H + 32 * ob + 4 * h;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x4 v;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) v[u] = tn::apply_act(acc[bq][4 * q + u], a.out_act);
-                    if (valid) *reinterpret_cast<f32x4 *>(yr + 8 * q) = v;
-                }
-            } else if (32 * ob < a.N) {
-                float *outp = stash + (tile * a.rows_total + a.off_out + 32 * ob + 4 * h) * 32 + j;
-                const int64_t row = tile * 32 + j;
-                const bool valid = row < n;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int f = 32 * ob + 8 * q + 4 * h;
-                    f32x4 v;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const bool ok = valid && f + u < a.N;
-                        outp[(u + 8 * q) * 32] = ok ? acc[bq][4 * q + u] : 0.0f;
-                        v[u] = tn::apply_act(acc[bq][4 * q + u], a.out_act);
-                    }
-                    if (valid) {
-                        if ((a.N & 3) == 0) { if (f < a.N) *reinterpret_cast<f32x4 *>(y + row * a.N + f) = v; }
-                        else {
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) if (f + u < a.N) y[row * a.N + f + u] = v[u];
-                        }
-                    }
-                }
-            }
+            } else if (a.N == H) emit_last_full<H, false>(a, n, stash, y, tile, ob, j, h, acc[bq]);      // (16 + 4 stores per block: tile_barrier<20 BPW>)
+            else if (32 * ob < a.N) emit_last_narrow(a, n, stash, y, tile, ob, j, h, acc[bq]);
         }
         if constexpr (!LAST) {
             if (a.off_bits >= 0) {                  // (wave-uniform) ReLU bits of the wave's blocks for the data-gradient kernel
@@ -377,7 +291,8 @@ __global__ __launch_bounds__(B3Geom<H>::THREADS) void dgrad_b3_kernel(DgradArgs 
     const int j = st.j, h = st.h, lane = st.lane;
     Op A[BPW][KS];
 #pragma unroll
-    for (int bq = 0; bq < BPW; ++bq) load_weights_cols<KS>(a.W, a.K, 32 * (BPW * st.wib + bq) + j, h, A[bq]);
+    for (int bq = 0; bq < BPW; ++bq)
+        read_weight_cols<KS>(a.W, a.K, 32 * (BPW * st.wib + bq) + j, h, [&](int s, const float (&v)[8]) { A[bq][s] = tn::b3::split8(v); });
     st.prologue(stash, a.rows_total, a.off_gin);
     int cur = 0;
 #pragma clang loop unroll(disable)
@@ -428,9 +343,9 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
     constexpr int RS = 24;                             // bf16 elements per LDS row: 16 samples + 8 pad = 48 B (3 x 16 B: odd)
     constexpr int PLANE = NR * RS;                     // bf16 elements per term plane
     constexpr int BUF = 3 * PLANE;                     // ... per buffer
-    constexpr int NCH = (NR * 4) / TH;                 // 16-byte chunks (4 samples of a row) per thread and half tile
+    using Chunks = WgradChunks<H, TH, RS>;
+    constexpr int NCH = Chunks::NCH;                   // 16-byte chunks (4 samples of a row) per thread and half tile
     constexpr int WK = (H / 32) / BK;                  // waves along k
-    static_assert(NCH * TH == NR * 4 && NCH >= 2 && (NCH & 1) == 0, "the waves own all tiles, every thread holds G and A chunks");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     unsigned short *lds = reinterpret_cast<unsigned short *>(lds_raw);
     const int lane = tn::lane_id(), i = lane & 31, h = lane >> 5;
@@ -444,31 +359,13 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
         for (int bk = 0; bk < BK; ++bk)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[bn][bk][r] = 0.0f;
-    // this thread's chunks of a half tile: chunk id = threadIdx.x + TH c -> row id / 4, samples 4 (id % 4) .. + 3 of the half
-    const int qd = threadIdx.x & 3;
-    int src_off[NCH], dst_off[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int row = (threadIdx.x + TH * c) >> 2;
-        src_off[c] = (row < H ? row : row - H) * 32 + 4 * qd;          // relative to the tile's G rows (c < NCH / 2) / A rows
-        dst_off[c] = row * RS + 4 * qd;
-    }
+    Chunks ch;
+    ch.init();
     float dbacc[NCH / 2];
 #pragma unroll
     for (int c = 0; c < NCH / 2; ++c) dbacc[c] = 0.0f;
-    const int64_t n_half = 2 * n_tiles;                           // half tile t: tile t / 2, samples 16 (t & 1) .. + 15
-    const int64_t stride = gridDim.x;                             // tiles are dealt round-robin to the workgroups
-    struct Bases { const global_char *g, *a; };                   // wave-uniform: the half tile's G rows and A rows
-    auto half_src = [&](int64_t it) {                             // `it`-th half tile of this workgroup
-        int64_t tile = blockIdx.x + (it >> 1) * stride;
-        tile = tile < n_tiles ? tile : n_tiles - 1;
-        return Bases{wave_uniform_global(stash + (tile * a.rows_total + a.off_g) * 32 + 16 * (it & 1)),
-                     wave_uniform_global(stash + (tile * a.rows_total + a.off_a) * 32 + 16 * (it & 1))};
-    };
-    const int64_t my_tiles = (int64_t)blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + stride - 1) / stride : 0;
-    const int64_t iters = 2 * my_tiles;
+    const int64_t iters = wgrad_half_tiles(n_tiles);
     if (iters == 0) return;
-    (void)n_half;
     // The half tile in flight lives in ONE register set: chunk c of half tile k + 1 is requested right behind the conversion of
     // chunk c of half tile k (its registers are free at that moment) and consumed one half tile later -- a whole iteration
     // (~3000 matrix-pipe cycles) for every load, and at each conversion exactly NCH - 1 younger loads are outstanding, so the
@@ -476,11 +373,8 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
     // of every half tile; a 64-bit address per lane makes it build the address in the load's destination registers: the
     // loads take the SGPR-base form, wave-uniform base + the thread's 32-bit byte offset.)
     f32x4 st[NCH];
-    unsigned src_boff[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) src_boff[c] = (unsigned)src_off[c] * 4u;
-    auto load_chunk = [&](const Bases &base, int c) {
-        unsigned off = src_boff[c];
+    auto load_chunk = [&](const HalfBases &base, int c) {
+        unsigned off = ch.src_boff[c];
         asm volatile("" : "+v"(off));                          // (keeps the zero-extension at the access: SGPR-base form)
         st[c] = *reinterpret_cast<const __attribute__((address_space(1))) f32x4 *>((c < NCH / 2 ? base.g : base.a) + off);
     };
@@ -488,7 +382,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
         unsigned h0, m0, l0, h1, m1, l1;
         tn::b3::split2(st[c][0], st[c][1], h0, m0, l0);
         tn::b3::split2(st[c][2], st[c][3], h1, m1, l1);
-        unsigned short *d = buf + dst_off[c];
+        unsigned short *d = buf + ch.dst_off[c];
         *reinterpret_cast<uint2 *>(d) = make_uint2(h0, h1);
         *reinterpret_cast<uint2 *>(d + PLANE) = make_uint2(m0, m1);
         *reinterpret_cast<uint2 *>(d + 2 * PLANE) = make_uint2(l0, l1);
@@ -501,7 +395,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
     // behind every MFMA.
     unsigned cu[8];          // conversion state carried between micro-steps
     float cf[4];
-    auto micro = [&](int c, int m, unsigned short *buf, const Bases &nb) {
+    auto micro = [&](int c, int m, unsigned short *buf, const HalfBases &nb) {
         const unsigned MSK = 0xffff0000u;
         const int e = m >= 5 ? 2 : 0;                        // value pair (e, e + 1) of the chunk
         const int mm = m >= 5 ? m - 5 : m;
@@ -518,7 +412,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
                 if (q == 0) { cu[4] = cu[0]; cu[5] = cu[2]; cu[6] = cu[1]; }      // keep the first pair's (hi, mid, lo) for the 8-byte writes
             }
         } else if (m == 10) {
-            unsigned short *d = buf + dst_off[c];
+            unsigned short *d = buf + ch.dst_off[c];
             *reinterpret_cast<uint2 *>(d) = make_uint2(cu[4], cu[0]);
             *reinterpret_cast<uint2 *>(d + PLANE) = make_uint2(cu[5], cu[2]);
             *reinterpret_cast<uint2 *>(d + 2 * PLANE) = make_uint2(cu[6], cu[1]);
@@ -529,7 +423,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
     };
     // prologue: half tile 0 converted, half tile 1 in registers
     {
-        const Bases b0 = half_src(0), b1 = half_src(1);
+        const HalfBases b0 = half_src(a, stash, n_tiles, 0), b1 = half_src(a, stash, n_tiles, 1);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) load_chunk(b0, c);
 #pragma unroll
@@ -537,10 +431,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
     }
     __syncthreads();
     int g_off[BN], a_off[BK];
-#pragma unroll
-    for (int bn = 0; bn < BN; ++bn) g_off[bn] = (32 * (tn0 + bn) + i) * RS + 8 * h;
-#pragma unroll
-    for (int bk = 0; bk < BK; ++bk) a_off[bk] = (H + 32 * (tk0 + bk) + i) * RS + 8 * h;
+    wgrad_operand_offsets<H, RS>(tn0, tk0, i, h, g_off, a_off);
     auto read_op = [&](const unsigned short *buf, int off) {
         Op o;
         o.hi = *reinterpret_cast<const u32x4 *>(buf + off);
@@ -556,7 +447,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
         constexpr bool CONVERT = decltype(convert_tag)::value;
         const unsigned short *bc = lds + cur * BUF;
         unsigned short *bnx = lds + (cur ^ 1) * BUF;
-        const Bases nb = half_src(it + 2 < iters ? it + 2 : it);     // (clamped: loaded, never used)
+        const HalfBases nb = half_src(a, stash, n_tiles, it + 2 < iters ? it + 2 : it);     // (clamped: loaded, never used)
         Op gop[BN];
 #pragma unroll
         for (int bn = 0; bn < BN; ++bn) gop[bn] = read_op(bc, g_off[bn]);
@@ -610,66 +501,8 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_b3_k
     // (all MFMA results are complete before the first accumulator read whichever way the loop was left: see tn::pin16 for the
     // hipcc wait-state bug; pinning 256 accumulator registers in VGPRs at once is not an option here)
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-#pragma unroll
-    for (int bn = 0; bn < BN; ++bn)
-#pragma unroll
-        for (int bk = 0; bk < BK; ++bk) {
-            const int k = 32 * (tk0 + bk) + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = 32 * (tn0 + bn) + frow(r, h);
-                atomicAdd(&a.gW[(int64_t)nn * a.K + k], acc[bn][bk][r]);
-            }
-        }
-    // bias gradient: the four threads of a row (quarters of the 16 samples) are neighbours
-#pragma unroll
-    for (int c = 0; c < NCH / 2; ++c) {
-        float sgm = dbacc[c];
-        sgm += __shfl_xor(sgm, 1, 64);
-        sgm += __shfl_xor(sgm, 2, 64);
-        const int row = (threadIdx.x + TH * c) >> 2;
-        if (qd == 0) atomicAdd(&a.gB[row], sgm);
-    }
-}
-
-template <int H, int BN, int BK>
-int launch_wgrad(const WgradArgs &w, int64_t n, const float *stash, hipStream_t s)
-{
-    constexpr size_t lds_bytes = (size_t)2 * 3 * (2 * H) * 24 * 2;
-    auto kern = wgrad_b3_kernel<H, BN, BK>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd(bf16x3): cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int per_cu = lds_bytes * 2 <= (size_t)LDS_LIMIT_BYTES ? 2 : 1;
-    kern<<<dim3((unsigned)std::min<int64_t>(n_tiles, 256 * per_cu)), dim3(64 * (H / 32 / BN) * (H / 32 / BK)), lds_bytes, s>>>(w, n, stash);
-    return tn::check_launch("wgrad_b3_kernel");
-}
-
-template <int H, bool LAST>
-int launch_fwd(const FwdLayerArgs &f, int64_t n, float *stash, float *y, hipStream_t s)
-{
-    using G = B3Geom<H>;
-    auto kern = fwd_b3_kernel<H, LAST>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_fwd(bf16x3): cannot reserve %zu B of LDS: %s", G::lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + G::STREAMS - 1) / G::STREAMS, 256));
-    kern<<<dim3((unsigned)bl), dim3(G::THREADS), G::lds_bytes, s>>>(f, n, stash, y);
-    return tn::check_launch("fwd_b3_kernel");
-}
-
-template <int H>
-int launch_dgrad(const DgradArgs &d, int64_t n, float *stash, hipStream_t s)
-{
-    using G = B3Geom<H>;
-    if (d.off_bits < 0) return tn::fail(TN_E_CONFIG, "mlp_bwd(bf16x3): the data gradient takes its ReLU masks as bit rows");
-    auto kern = dgrad_b3_kernel<H>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd(bf16x3): cannot reserve %zu B of LDS: %s", G::lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + G::STREAMS - 1) / G::STREAMS, 256));
-    kern<<<dim3((unsigned)bl), dim3(G::THREADS), G::lds_bytes, s>>>(d, n, stash);
-    return tn::check_launch("dgrad_b3_kernel");
+    flush_tiles<false>(a, tn0, tk0, i, h, acc, 1.0f);
+    flush_bias<TH>(a.gB, dbacc);
 }
 
 }  // namespace
@@ -679,27 +512,36 @@ namespace layers {
 
 __attribute__((visibility("hidden"))) int launch_fwd_b3(int H, bool last, const FwdLayerArgs &f, int64_t n, float *stash, float *y, hipStream_t s)
 {
-    if (H == 256) return last ? launch_fwd<256, true>(f, n, stash, y, s) : launch_fwd<256, false>(f, n, stash, y, s);
-    if (H == 128) return last ? launch_fwd<128, true>(f, n, stash, y, s) : launch_fwd<128, false>(f, n, stash, y, s);
-    return tn::fail(TN_E_CONFIG, "mlp_fwd(bf16x3): width 128 or 256");
+    return for_width(H, "mlp_fwd(bf16x3): width 128 or 256", [&](auto width) {
+        using G = B3Geom<decltype(width)::value>;
+        auto kern = last ? fwd_b3_kernel<decltype(width)::value, true> : fwd_b3_kernel<decltype(width)::value, false>;
+        return launch(kern, G::THREADS / 64, G::lds_bytes, stream_blocks(n, G::STREAMS), s, "mlp_fwd(bf16x3): fwd_b3_kernel", f, n, stash, y);
+    });
 }
 
 __attribute__((visibility("hidden"))) int launch_dgrad_b3(int H, const DgradArgs &d, int64_t n, float *stash, hipStream_t s)
 {
-    if (H == 256) return launch_dgrad<256>(d, n, stash, s);
-    if (H == 128) return launch_dgrad<128>(d, n, stash, s);
-    return tn::fail(TN_E_CONFIG, "mlp_bwd(bf16x3): width 128 or 256");
+    if (d.off_bits < 0) return tn::fail(TN_E_CONFIG, "mlp_bwd(bf16x3): the data gradient takes its ReLU masks as bit rows");
+    return for_width(H, "mlp_bwd(bf16x3): width 128 or 256", [&](auto width) {
+        using G = B3Geom<decltype(width)::value>;
+        return launch(dgrad_b3_kernel<decltype(width)::value>, G::THREADS / 64, G::lds_bytes, stream_blocks(n, G::STREAMS), s,
+                      "mlp_bwd(bf16x3): dgrad_b3_kernel", d, n, stash);
+    });
 }
 
-__attribute__((visibility("hidden"))) int launch_wgrad_b3(int H, const WgradArgs &w, int64_t n, const float *stash, hipStream_t s)
-{
-    if (w.first || w.N != H || w.K != H) return tn::fail(TN_E_CONFIG, "mlp_bwd(bf16x3): square hidden layers only");
 #ifndef TN_B3_WGRAD_BK256
 #define TN_B3_WGRAD_BK256 2
 #endif
-    if (H == 256) return launch_wgrad<256, 4, TN_B3_WGRAD_BK256>(w, n, stash, s);
-    if (H == 128) return launch_wgrad<128, 2, 2>(w, n, stash, s);
-    return tn::fail(TN_E_CONFIG, "mlp_bwd(bf16x3): width 128 or 256");
+__attribute__((visibility("hidden"))) int launch_wgrad_b3(int H, const WgradArgs &w, int64_t n, const float *stash, hipStream_t s)
+{
+    if (w.first || w.N != H || w.K != H) return tn::fail(TN_E_CONFIG, "mlp_bwd(bf16x3): square hidden layers only");
+    return for_width(H, "mlp_bwd(bf16x3): width 128 or 256", [&](auto width) {
+        constexpr int W = decltype(width)::value, BN = W == 256 ? 4 : 2, BK = W == 256 ? TN_B3_WGRAD_BK256 : 2;
+        constexpr size_t lds_bytes = (size_t)2 * 3 * (2 * W) * 24 * 2;
+        const int per_cu = lds_bytes * 2 <= (size_t)LDS_LIMIT_BYTES ? 2 : 1;
+        return launch(wgrad_b3_kernel<W, BN, BK>, (W / 32 / BN) * (W / 32 / BK), lds_bytes, grid_blocks(n, 1, 256 * per_cu), s,
+                      "mlp_bwd(bf16x3): wgrad_b3_kernel", w, n, stash);
+    });
 }
 
 }  // namespace layers

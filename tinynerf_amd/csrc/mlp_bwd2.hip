@@ -57,6 +57,7 @@ namespace {
 
 using tn::f32x16;
 using tn::f32x4;
+using tn::act_grad;
 using namespace tn::mlp;
 
 template <int N, class F>
@@ -65,12 +66,6 @@ __device__ __forceinline__ void static_for(F &&f) {
         static_for<N - 1>(f);
         f(std::integral_constant<int, N - 1>{});
     }
-}
-
-__device__ __forceinline__ float act_grad(float pre, int act) {
-    if (act == TN_ACT_EXP_M1) return expf(fminf(fmaxf(pre - 1.0f, -15.0f), 15.0f));     // models.py:50-53
-    if (act == TN_ACT_SIGMOID) { const float s = 1.0f / (1.0f + expf(-pre)); return s * (1.0f - s); }
-    return 1.0f;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -23,13 +23,10 @@ using tn::f32x4;
 using namespace tn::mlp;
 using namespace tn::layers;
 
-__device__ __forceinline__ float act_grad(float pre, int act) {
-    if (act == TN_ACT_EXP_M1) return expf(fminf(fmaxf(pre - 1.0f, -15.0f), 15.0f));     // models.py:50-53
-    if (act == TN_ACT_SIGMOID) { const float s = 1.0f / (1.0f + expf(-pre)); return s * (1.0f - s); }
-    return 1.0f;
-}
+using tn::act_grad;
 
-__device__ __forceinline__ void store_rows(float *__restrict__ rows, const f32x16 &t, int ob, int j, int h) {
+// D-layout tile -> rows [feature][32 samples], one 64-bit address per lane (tn::mlp::store_rows is the SGPR-base form)
+__device__ __forceinline__ void store_rows_lane(float *__restrict__ rows, const f32x16 &t, int ob, int j, int h) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) rows[(32 * ob + frow(r, h)) * 32 + j] = t[r];
 }
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(WPB * 64) void fwd_stash_kernel(MlpArgs a, const fl
         for (int ob = 0; ob < T; ++ob) {
             tn::pin16(act[ob]);
             act[ob] = tn::relu16(act[ob]);
-            store_rows(st, act[ob], ob, j, h);
+            store_rows_lane(st, act[ob], ob, j, h);
         }
         if constexpr (FIRST_ONLY) {                // the remaining layers run as layer-kernel launches
             // ReLU bits of this activation where the layer kernels keep them (two rows per 32-feature block), so that the data
@@ -143,7 +140,7 @@ __global__ __launch_bounds__(WPB * 64) void fwd_stash_kernel(MlpArgs a, const fl
         for (int l = 1; l + 1 < L; ++l) {
             tn::hidden_layer<H>(a.W[l], a.B[l], H, act, j, h);
 #pragma unroll
-            for (int ob = 0; ob < T; ++ob) store_rows(st + l * H * 32, act[ob], ob, j, h);
+            for (int ob = 0; ob < T; ++ob) store_rows_lane(st + l * H * 32, act[ob], ob, j, h);
         }
         // output layer -> g = gy * act'(pre) as rows [out feature][32 samples]
         const float *Wf = a.W[L - 1];
@@ -540,14 +537,11 @@ __global__ __launch_bounds__(512) void fwd_wreg_kernel(FwdLayerArgs a, int64_t n
     using G = WregGeom<H>;
     constexpr int T = G::T, SW = G::SW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = tn::lane_id(), j = lane & 31, h = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int stream = wave / T, ob = wave % T;
-    float *buf = lds + stream * 3 * G::TILE;
-    const int64_t n_tiles = (n + 31) >> 5;
-    const int64_t stride = (int64_t)gridDim.x * G::STREAMS;
-    const int64_t first = (int64_t)blockIdx.x * G::STREAMS;          // the workgroup's lowest tile: defines its iteration count
-    const int64_t iters = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
+    TileWalk<G::STREAMS, T> tw;
+    tw.init(n);
+    const int lane = tw.lane, j = tw.j, h = tw.h, ob = tw.wib;
+    float *buf = lds + tw.stream * 3 * G::TILE;
+    const int64_t iters = tw.iters;
     if (iters == 0) return;
     // A operands: W[32 ob + j][32 t + 8 q + 4 h .. + 3]
     f32x4 W[T][4];
@@ -565,11 +559,10 @@ __global__ __launch_bounds__(512) void fwd_wreg_kernel(FwdLayerArgs a, int64_t n
     f32x16 bias;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { const int f = 32 * ob + frow(r, h); bias[r] = a.B[f < a.N ? f : 0]; }
-    auto tile_of = [&](int64_t it) { const int64_t t = first + stream + it * stride; return t < n_tiles ? t : n_tiles - 1; };
     float stage[16];
-    wreg_load_rows(urow(stash, tile_of(0) * a.rows_total + a.off_in), ob, j, h, stage);
+    wreg_load_rows(urow(stash, tw.tile_of(0) * a.rows_total + a.off_in), ob, j, h, stage);
     wreg_write_rows(buf, SW, ob, j, h, stage);
-    wreg_load_rows(urow(stash, tile_of(1) * a.rows_total + a.off_in), ob, j, h, stage);
+    wreg_load_rows(urow(stash, tw.tile_of(1) * a.rows_total + a.off_in), ob, j, h, stage);
     __syncthreads();
     // results of a tile: [feature][32 samples] rows (+ y for the last layer).  A stream past the end recomputes the last tile
     // (same inputs -> same values) rather than branching around its stores.
@@ -581,29 +574,7 @@ __global__ __launch_bounds__(512) void fwd_wreg_kernel(FwdLayerArgs a, int64_t n
                     unsigned *bits = reinterpret_cast<unsigned *>(urow(stash, tile * a.rows_total + a.off_bits + 2 * ob));
                     bits[lane] = relu_bits(acc);
                 }
-            } else {
-                float *outp = stash + (tile * a.rows_total + a.off_out + 32 * ob + 4 * h) * 32 + j;
-                const int64_t row = tile * 32 + j;
-                const bool valid = row < n;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int f = 32 * ob + 8 * q + 4 * h;
-                    f32x4 v;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const bool ok = valid && f + u < a.N;
-                        outp[(u + 8 * q) * 32] = ok ? acc[4 * q + u] : 0.0f;
-                        v[u] = tn::apply_act(acc[4 * q + u], a.out_act);
-                    }
-                    if (valid) {
-                        if ((a.N & 3) == 0) { if (f < a.N) *reinterpret_cast<f32x4 *>(y + row * a.N + f) = v; }
-                        else {
-#pragma unroll
-                            for (int u = 0; u < 4; ++u) if (f + u < a.N) y[row * a.N + f + u] = v[u];
-                        }
-                    }
-                }
-            }
+            } else emit_last_narrow(a, n, stash, y, tile, ob, j, h, acc);
         }
     };
     int cur = 0;
@@ -617,8 +588,8 @@ __global__ __launch_bounds__(512) void fwd_wreg_kernel(FwdLayerArgs a, int64_t n
         // VMEM queue order: the PREVIOUS tile's stores, then the requests for tile it+2 -- the s_waitcnt vmcnt in front of the
         // next iteration's ds_write then waits for exactly these loads (stores issued after them would have to drain first:
         // vmcnt counts loads and stores in one in-order queue on gfx9)
-        if (it > 0) emit(tile_of(it - 1), res);
-        wreg_load_rows(urow(stash, tile_of(it + 2) * a.rows_total + a.off_in), ob, j, h, stage);
+        if (it > 0) emit(tw.tile_of(it - 1), res);
+        wreg_load_rows(urow(stash, tw.tile_of(it + 2) * a.rows_total + a.off_in), ob, j, h, stage);
         __builtin_amdgcn_sched_barrier(0);
         const float *bt = buf + cur * G::TILE + j * SW + 4 * h;
         f32x16 acc = bias;
@@ -632,7 +603,7 @@ __global__ __launch_bounds__(512) void fwd_wreg_kernel(FwdLayerArgs a, int64_t n
         if constexpr (!LAST) res = tn::relu16(acc); else res = acc;
         cur = nxt;
     }
-    emit(tile_of(iters - 1), res);
+    emit(tw.tile_of(iters - 1), res);
 }
 
 // data gradient twin: wave `kb` owns input-feature block kb and holds W[0 .. H)[32 kb .. 32 kb + 31] (W^T rows) in registers
@@ -642,14 +613,11 @@ __global__ __launch_bounds__(512) void dgrad_wreg_kernel(DgradArgs a, int64_t n,
     using G = WregGeom<H>;
     constexpr int T = G::T, SW = G::SW;
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int lane = tn::lane_id(), j = lane & 31, h = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int stream = wave / T, kb = wave % T;
-    float *buf = lds + stream * 3 * G::TILE;
-    const int64_t n_tiles = (n + 31) >> 5;
-    const int64_t stride = (int64_t)gridDim.x * G::STREAMS;
-    const int64_t first = (int64_t)blockIdx.x * G::STREAMS;
-    const int64_t iters = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
+    TileWalk<G::STREAMS, T> tw;
+    tw.init(n);
+    const int lane = tw.lane, j = tw.j, h = tw.h, kb = tw.wib;
+    float *buf = lds + tw.stream * 3 * G::TILE;
+    const int64_t iters = tw.iters;
     if (iters == 0) return;
     // A operands: W[32 t + 8 q + 4 h + u][32 kb + j]   (N == K == H)
     f32x4 W[T][4];
@@ -662,11 +630,10 @@ __global__ __launch_bounds__(512) void dgrad_wreg_kernel(DgradArgs a, int64_t n,
 #pragma unroll
                 for (int u = 0; u < 4; ++u) W[t][q][u] = wcol[(int64_t)(32 * t + 8 * q + u) * a.K];
     }
-    auto tile_of = [&](int64_t it) { const int64_t t = first + stream + it * stride; return t < n_tiles ? t : n_tiles - 1; };
     float stage[16];
-    wreg_load_rows(urow(stash, tile_of(0) * a.rows_total + a.off_gin), kb, j, h, stage);
+    wreg_load_rows(urow(stash, tw.tile_of(0) * a.rows_total + a.off_gin), kb, j, h, stage);
     wreg_write_rows(buf, SW, kb, j, h, stage);
-    wreg_load_rows(urow(stash, tile_of(1) * a.rows_total + a.off_gin), kb, j, h, stage);
+    wreg_load_rows(urow(stash, tw.tile_of(1) * a.rows_total + a.off_gin), kb, j, h, stage);
     __syncthreads();
     auto emit = [&](int64_t tile, const f32x16 &g) {
         wreg_store_block(urow(stash, tile * a.rows_total + a.off_gout), kb, j, h, g);
@@ -680,13 +647,13 @@ __global__ __launch_bounds__(512) void dgrad_wreg_kernel(DgradArgs a, int64_t n,
         const int nxt = cur == 2 ? 0 : cur + 1;
         wreg_write_rows(buf + nxt * G::TILE, SW, kb, j, h, stage);
         // VMEM queue order (see fwd_wreg_kernel): previous tile's stores, this tile's ReLU-mask rows, requests for tile it+2
-        if (it > 0) emit(tile_of(it - 1), res);
-        const int64_t tile = tile_of(it);
+        if (it > 0) emit(tw.tile_of(it - 1), res);
+        const int64_t tile = tw.tile_of(it);
         float m[16];
         unsigned mbits = 0;
         if (a.off_bits >= 0) mbits = reinterpret_cast<const unsigned *>(urow(stash, tile * a.rows_total + a.off_bits + 2 * kb))[lane];
         else wreg_load_block(urow(stash, tile * a.rows_total + a.off_mask), kb, j, h, m);
-        wreg_load_rows(urow(stash, tile_of(it + 2) * a.rows_total + a.off_gin), kb, j, h, stage);
+        wreg_load_rows(urow(stash, tw.tile_of(it + 2) * a.rows_total + a.off_gin), kb, j, h, stage);
         __builtin_amdgcn_sched_barrier(0);
         const float *bt = buf + cur * G::TILE + j * SW + 4 * h;
         f32x16 acc;
@@ -708,33 +675,21 @@ __global__ __launch_bounds__(512) void dgrad_wreg_kernel(DgradArgs a, int64_t n,
         }
         cur = nxt;
     }
-    emit(tile_of(iters - 1), res);
+    emit(tw.tile_of(iters - 1), res);
 }
 
 template <int H, bool LAST>
 int launch_fwd_wreg(const FwdLayerArgs &f, int64_t n, float *stash, float *y, hipStream_t s)
 {
     using G = WregGeom<H>;
-    auto kern = fwd_wreg_kernel<H, LAST>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_fwd: cannot reserve %zu B of LDS: %s", G::lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + G::STREAMS - 1) / G::STREAMS, 256));
-    kern<<<dim3((unsigned)bl), dim3(512), G::lds_bytes, s>>>(f, n, stash, y);
-    return tn::check_launch("fwd_wreg_kernel");
+    return launch(fwd_wreg_kernel<H, LAST>, 8, G::lds_bytes, stream_blocks(n, G::STREAMS), s, "mlp_fwd: fwd_wreg_kernel", f, n, stash, y);
 }
 
 template <int H>
 int launch_dgrad_wreg(const DgradArgs &d, int64_t n, float *stash, hipStream_t s)
 {
     using G = WregGeom<H>;
-    auto kern = dgrad_wreg_kernel<H>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", G::lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + G::STREAMS - 1) / G::STREAMS, 256));
-    kern<<<dim3((unsigned)bl), dim3(512), G::lds_bytes, s>>>(d, n, stash);
-    return tn::check_launch("dgrad_wreg_kernel");
+    return launch(dgrad_wreg_kernel<H>, 8, G::lds_bytes, stream_blocks(n, G::STREAMS), s, "mlp_bwd: dgrad_wreg_kernel", d, n, stash);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -842,12 +797,7 @@ __global__ __launch_bounds__(512) void wgrad_layer_kernel(WgradArgs a, const flo
 // LDS-direct load is lane-linear (no row padding possible), so the 16-byte chunks of a row are XOR-swizzled through the
 // SOURCE address: slot p of row r holds chunk p ^ ((r >> 1) & 7), which spreads the 16 rows of a ds_read_b128 phase over
 // all 64 banks.
-// global_load_lds_dwordx4: 16 bytes per lane from `src` (per lane) to LDS at `dst` (wave-uniform) + 16 * lane; counted in vmcnt.
-// (Kept in a __device__ function: the builtin inside a __global__ template makes hipcc's host pass drop the kernel's stub.)
-__device__ __forceinline__ void glds16(const float *src, float *dst) {
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-}
-
+// (LDS-direct loads: glds16, mlp_stage.h.)
 template <int H, int BN, int BK>
 __global__ __launch_bounds__(512) void wgrad_lds_kernel(WgradArgs a, int64_t n, const float *__restrict__ stash)
 {
@@ -927,19 +877,10 @@ __global__ __launch_bounds__(512) void wgrad_lds_kernel(WgradArgs a, int64_t n, 
         __syncthreads();                                   // (drains this wave's LDS-direct loads: the next tile is in place)
         cur ^= 1;
     }
+    flush_tiles<true>(a, tn0, tk0, i, h, acc, 1.0f);
+    if (tk0 == 0) {
 #pragma unroll
-    for (int bn = 0; bn < BN; ++bn) {
-#pragma unroll
-        for (int bk = 0; bk < BK; ++bk) {
-            tn::pin16(acc[bn][bk]);
-            const int k = 32 * (tk0 + bk) + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = 32 * (tn0 + bn) + frow(r, h);
-                atomicAdd(&a.gW[(int64_t)nn * a.K + k], acc[bn][bk][r]);
-            }
-        }
-        if (tk0 == 0) {
+        for (int bn = 0; bn < BN; ++bn) {
             float s = dbacc[bn];
             s += __shfl_xor(s, 32, 64);
             if (h == 0) atomicAdd(&a.gB[32 * (tn0 + bn) + i], s);
@@ -951,12 +892,7 @@ template <int H, int BN, int BK>
 int launch_wgrad_lds(const WgradArgs &w, int64_t n, const float *stash, hipStream_t s)
 {
     constexpr size_t lds_bytes = (size_t)2 * 2 * H * 32 * sizeof(float);
-    auto kern = wgrad_lds_kernel<H, BN, BK>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    kern<<<dim3((unsigned)std::min<int64_t>(n_tiles, 256)), dim3(512), lds_bytes, s>>>(w, n, stash);
-    return tn::check_launch("wgrad_lds_kernel");
+    return launch(wgrad_lds_kernel<H, BN, BK>, 8, lds_bytes, grid_blocks(n, 1, 256), s, "mlp_bwd: wgrad_lds_kernel", w, n, stash);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1032,13 +968,7 @@ int launch_dgrad_first(const DgradArgs &d, int64_t n, const float *stash, float 
 {
     constexpr int WPB = 8;
     constexpr size_t lds_bytes = (size_t)64 * (H + 4) * sizeof(float);
-    auto kern = dgrad_first_kernel<H, WPB>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int per_cu = std::max(1, std::min<int>((int)(160 * 1024 / lds_bytes), 2048 / (WPB * 64)));
-    kern<<<dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * per_cu))), dim3(WPB * 64), lds_bytes, s>>>(d, n, stash, gx);
-    return tn::check_launch("dgrad_first_kernel");
+    return launch(dgrad_first_kernel<H, WPB>, WPB, lds_bytes, grid_per_cu(n, WPB, lds_bytes), s, "mlp_bwd: dgrad_first_kernel", d, n, stash, gx);
 }
 
 template <int H, int T, int NOT>
@@ -1046,15 +976,10 @@ int launch_fwd_lds(const FwdLayerArgs &f, int64_t n, float *stash, float *y, hip
 {
     constexpr int WL = 8;
     constexpr size_t lds_bytes = (size_t)32 * NOT * (32 * T + 4) * 4;
-    auto kern = fwd_lds_kernel<H, T, NOT, WL>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_fwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int groups = (((f.N + 31) / 32) + NOT - 1) / NOT;
-    const int per_cu = lds_bytes * 2 <= 160 * 1024 ? 2 : 1;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + WL - 1) / WL, (256 * per_cu) / groups));
-    kern<<<dim3((unsigned)bl, (unsigned)groups), dim3(WL * 64), lds_bytes, s>>>(f, n, stash, y);
-    return tn::check_launch("fwd_lds_kernel");
+    const int groups = (((f.N + 31) / 32) + NOT - 1) / NOT;                  // blockIdx.y: NOT output blocks each
+    const int per_cu = lds_bytes * 2 <= (size_t)LDS_LIMIT_BYTES ? 2 : 1;
+    return launch(fwd_lds_kernel<H, T, NOT, WL>, WL, lds_bytes, dim3((unsigned)grid_blocks(n, WL, (256 * per_cu) / groups), (unsigned)groups), s,
+                  "mlp_fwd: fwd_lds_kernel", f, n, stash, y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1420,14 +1345,10 @@ int run_bwd(const Plan &p, const MlpArgs &a, const float *x, const float *aux, c
             if constexpr (H >= 128) {
                 constexpr int NKT = 4, WL = 8;
                 constexpr size_t lds_bytes = (size_t)32 * NKT * (H + 4) * 4;
-                auto kern = dgrad_lds_kernel<H, NKT, WL>;
-                hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-                if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
                 const int groups = (H / 32) / NKT;
-                const int per_cu = lds_bytes * 2 <= 160 * 1024 ? 2 : 1;
-                const int64_t bl = std::min<int64_t>((n_tiles + WL - 1) / WL, (256 * per_cu) / groups);
-                kern<<<dim3((unsigned)bl, (unsigned)groups), dim3(WL * 64), lds_bytes, s>>>(d, n, stash);
-                rc = tn::check_launch("dgrad_lds_kernel");
+                const int per_cu = lds_bytes * 2 <= (size_t)LDS_LIMIT_BYTES ? 2 : 1;
+                rc = launch(dgrad_lds_kernel<H, NKT, WL>, WL, lds_bytes, dim3((unsigned)grid_blocks(n, WL, (256 * per_cu) / groups), (unsigned)groups), s,
+                            "mlp_bwd: dgrad_lds_kernel", d, n, stash);
             }
             break;
         case Dgrad::GENERAL:

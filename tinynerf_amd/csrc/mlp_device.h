@@ -22,6 +22,8 @@ namespace tn {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+__device__ __forceinline__ int frow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }     // D-layout row of reg r
+
 __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
 }
@@ -121,6 +123,13 @@ __device__ __forceinline__ float apply_act(float y, int act) {
     if (act == TN_ACT_EXP_M1) return expf(y - 1.0f);                 // models.py:74, truncated_exp fwd = exp
     if (act == TN_ACT_SIGMOID) return 1.0f / (1.0f + expf(-y));      // models.py:85
     return y;
+}
+
+// d act / d pre of the output activation
+__device__ __forceinline__ float act_grad(float pre, int act) {
+    if (act == TN_ACT_EXP_M1) return expf(fminf(fmaxf(pre - 1.0f, -15.0f), 15.0f));     // models.py:50-53
+    if (act == TN_ACT_SIGMOID) { const float s = 1.0f / (1.0f + expf(-pre)); return s * (1.0f - s); }
+    return 1.0f;
 }
 
 // positional-encoding value of flat index p for one point (models.py:36-39):

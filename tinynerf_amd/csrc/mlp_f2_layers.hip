@@ -20,7 +20,8 @@
 //
 // Structure, geometry and instruction scheduling follow mlp_b3_layers.hip (a wave owns one 32-row block of the output with its
 // weights in registers, eight waves per stream at H = 256 / four at H = 128, LDS-direct staging, conversion micro-steps pinned
-// behind the MFMAs of the first half of the k loop).
+// behind the MFMAs of the first half of the k loop); what the two files hold in common -- tile walk, weight readers, the last layer's
+// epilogues, the weight gradient's chunk tables and flush -- is written once in mlp_layers.h.
 #include "mlp_layers.h"
 #include "b3_device.h"
 #include <algorithm>
@@ -51,9 +52,6 @@ struct Op2 { u32x4 hi, lo; };            // 8 values as two packed-fp16 operands
 #ifndef TN_F2_NT
 #define TN_F2_NT 3
 #endif
-__device__ __forceinline__ void glds16(const float *src, float *dst) {
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, (TN_F2_NT & 1) ? 2 : 0);      // aux bit 1 = nt
-}
 __device__ __forceinline__ f32x16 mfma_h(const u32x4 &a, const u32x4 &b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
@@ -100,13 +98,6 @@ __device__ __forceinline__ Op2 read_b2(const unsigned short *tile, int j, int h,
     return o;
 }
 
-template <int NROWS>
-__device__ __forceinline__ void request_rows(const float *rows, int r0, float *stage, int lane) {
-    const float *src = rows + r0 * 32 + 4 * lane;            // 16 B per lane: one instruction = 8 rows x 128 B
-#pragma unroll
-    for (int e = 0; e < NROWS / 8; ++e) glds16(src + e * 256, stage + e * 256);
-}
-
 // A operands of one 32-row block, all KS steps, scaled by `s` (a power of two)
 template <int KS>
 __device__ __forceinline__ void split_weights(const float (&v)[KS][8], float s, Op2 (&A)[KS]) {
@@ -121,38 +112,31 @@ __device__ __forceinline__ void split_weights(const float (&v)[KS][8], float s, 
 }
 
 template <int H>
-struct Stream2 {
+struct Stream2 : TileWalk<F2Geom<H>::STREAMS, F2Geom<H>::WPS> {
     using G = F2Geom<H>;
+    using Walk = TileWalk<G::STREAMS, G::WPS>;
+    using Walk::lane; using Walk::j; using Walk::h; using Walk::wave; using Walk::stream; using Walk::wib; using Walk::tile_of;
     static constexpr int KS = G::KS, SB = G::SB, PLANE = G::PLANE;
-    int lane, j, h, wave, stream, wib;
     unsigned short *tiles;
     float *stage0;                              // this stream's two staging buffers
     float *pm;                                  // this stream's two column-maximum slots
     float *red;                                 // workgroup scratch (prologue: layer maximum)
     float seen;                                 // largest |value| this lane has staged so far (-> the weight gradient's scale)
-    int64_t n_tiles, stride, first, iters;
 
     __device__ __forceinline__ void init(unsigned char *lds_raw, int64_t n) {
-        lane = tn::lane_id(); j = lane & 31; h = lane >> 5;
-        wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        stream = wave / G::WPS; wib = wave % G::WPS;
+        Walk::init(n);
         seen = 0.0f;
         unsigned char *sbase = lds_raw + stream * G::STREAM_B;
         tiles = reinterpret_cast<unsigned short *>(sbase);
         stage0 = reinterpret_cast<float *>(sbase + 2 * G::TILE_B);
         pm = stage0 + 2 * G::STAGE_F;
         red = reinterpret_cast<float *>(lds_raw + G::STREAMS * G::STREAM_B + H * 4);
-        n_tiles = (n + 31) >> 5;
-        stride = (int64_t)gridDim.x * G::STREAMS;
-        first = (int64_t)blockIdx.x * G::STREAMS;
-        iters = first < n_tiles ? (n_tiles - first + stride - 1) / stride : 0;
     }
-    __device__ __forceinline__ int64_t tile_of(int64_t it) const { const int64_t t = first + stream + it * stride; return t < n_tiles ? t : n_tiles - 1; }
     __device__ __forceinline__ float *stage(int sbuf) const { return stage0 + sbuf * G::STAGE_F + (32 * wib) * 32; }      // this wave's 32 rows
     __device__ __forceinline__ const float *sp(int sbuf) const { return stage(sbuf) + (16 * h) * 32 + j; }
     __device__ __forceinline__ unsigned short *np(int buf) const { return tiles + buf * (2 * PLANE) + j * SB + 32 * wib + 16 * h; }
     __device__ __forceinline__ void request(const float *stash, int64_t tile, int rows_total, int off, int sbuf) const {
-        request_rows<32>(urow(stash, tile * rows_total + off), 32 * wib, stage(sbuf), lane);
+        request_rows<32, (TN_F2_NT & 1) != 0>(urow(stash, tile * rows_total + off), 32 * wib, stage(sbuf), lane);
     }
     // largest |value| of this wave's 32 staged rows per sample -> pm[slot][sample][wave]
     __device__ __forceinline__ void publish_max(int sbuf) {
@@ -315,29 +299,13 @@ struct Stream2 {
     }
 };
 
-// weights of output rows 32 ob + i: step s, lane (i, h): W[row][16 s + 8 h + 0..7]   (forward)
+// use() of read_weight_rows / read_weight_cols: keeps the block's weights and their largest |value| (-> the layer's scale)
 template <int KS>
-__device__ __forceinline__ float load_rows(const float *__restrict__ W, int ldw, int row, bool ok, int h, float (&v)[KS][8]) {
-    const float *wr = W + (int64_t)(ok ? row : 0) * ldw + 8 * h;
-    float m = 0.0f;
+__device__ __forceinline__ auto keep_weights(float (&v)[KS][8], float &m) {
+    return [&](int s, const float (&t)[8]) {
 #pragma unroll
-    for (int s = 0; s < KS; ++s) {
-        const f32x4 w0 = *reinterpret_cast<const f32x4 *>(wr + 16 * s), w1 = *reinterpret_cast<const f32x4 *>(wr + 16 * s + 4);
-        const float t[8] = {w0[0], w0[1], w0[2], w0[3], w1[0], w1[1], w1[2], w1[3]};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { v[s][e] = ok ? t[e] : 0.0f; m = fmaxf(m, fabsf(v[s][e])); }
-    }
-    return m;
-}
-// ... of W^T: A[i = column 32 kb + i][k = row n]: step s, lane (i, h): W[16 s + 8 h + e][col]   (data gradient)
-template <int KS>
-__device__ __forceinline__ float load_cols(const float *__restrict__ W, int ldw, int col, int h, float (&v)[KS][8]) {
-    float m = 0.0f;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) { v[s][e] = W[(int64_t)(16 * s + 8 * h + e) * ldw + col]; m = fmaxf(m, fabsf(v[s][e])); }
-    return m;
+        for (int e = 0; e < 8; ++e) { v[s][e] = t[e]; m = fmaxf(m, fabsf(t[e])); }
+    };
 }
 
 template <int H, bool LAST>
@@ -357,7 +325,8 @@ __global__ __launch_bounds__(F2Geom<H>::THREADS) void fwd_f2_kernel(FwdLayerArgs
     {
         float v[KS][8];
         const int row = 32 * ob + j;
-        const float wmax = load_rows<KS>(a.W, a.K, row, row < a.N, h, v);
+        float wmax = 0.0f;
+        read_weight_rows<KS>(a.W, a.K, row, row < a.N, h, keep_weights<KS>(v, wmax));
         float s_w;
         st.layer_scale(wmax, s_w, inv_w);                    // (carries the barrier behind the bias staging)
         split_weights<KS>(v, s_w, A);
@@ -397,46 +366,8 @@ __global__ __launch_bounds__(F2Geom<H>::THREADS) void fwd_f2_kernel(FwdLayerArgs
                 unsigned *bits = reinterpret_cast<unsigned *>(urow(stash, tile * a.rows_total + a.off_bits + 2 * ob));
                 bits[lane] = relu_bits(acc);
             }
-        } else if (a.N == H) {
-            const int64_t row = tile * 32 + j;
-            const bool valid = row < n;
-            f32x16 pre;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) pre[r] = valid ? acc[r] : 0.0f;
-            wreg_store_block(urow(stash, tile * a.rows_total + a.off_out), ob, j, h, pre);
-            if (y != nullptr) {                      // (TN_MLP_ROWS_ONLY: the consumer reads the rows)
-                float *yr = y + (valid ? row : 0) * H + 32 * ob + 4 * h;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    f32x4 v;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) v[u] = tn::apply_act(acc[4 * q + u], a.out_act);
-                    if (valid) *reinterpret_cast<f32x4 *>(yr + 8 * q) = v;
-                }
-            }
-        } else if (32 * ob < a.N) {
-            float *outp = stash + (tile * a.rows_total + a.off_out + 32 * ob + 4 * h) * 32 + j;
-            const int64_t row = tile * 32 + j;
-            const bool valid = row < n;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int f = 32 * ob + 8 * q + 4 * h;
-                f32x4 v;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const bool ok = valid && f + u < a.N;
-                    outp[(u + 8 * q) * 32] = ok ? acc[4 * q + u] : 0.0f;
-                    v[u] = tn::apply_act(acc[4 * q + u], a.out_act);
-                }
-                if (valid) {
-                    if ((a.N & 3) == 0) { if (f < a.N) *reinterpret_cast<f32x4 *>(y + row * a.N + f) = v; }
-                    else {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) if (f + u < a.N) y[row * a.N + f + u] = v[u];
-                    }
-                }
-            }
-        }
+        } else if (a.N == H) emit_last_full<H, true>(a, n, stash, y, tile, ob, j, h, acc);      // (y may be null: TN_MLP_ROWS_ONLY)
+        else if (32 * ob < a.N) emit_last_narrow(a, n, stash, y, tile, ob, j, h, acc);
         st.tile_barrier();
         inv_cur = inv_next;
         cur ^= 1;
@@ -458,7 +389,8 @@ __global__ __launch_bounds__(F2Geom<H>::THREADS) void dgrad_f2_kernel(DgradArgs 
     float inv_w;
     {
         float v[KS][8];
-        const float wmax = load_cols<KS>(a.W, a.K, 32 * kb + j, h, v);
+        float wmax = 0.0f;
+        read_weight_cols<KS>(a.W, a.K, 32 * kb + j, h, keep_weights<KS>(v, wmax));
         float s_w;
         st.layer_scale(wmax, s_w, inv_w);
         split_weights<KS>(v, s_w, A);
@@ -507,9 +439,9 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_f2_k
     constexpr int RS = 24;                             // fp16 elements per LDS row: 16 samples + 8 pad
     constexpr int PLANE = NR * RS;
     constexpr int BUF = 2 * PLANE;
-    constexpr int NCH = (NR * 4) / TH;                 // 16-byte chunks (4 samples of a row) per thread and half tile
+    using Chunks = WgradChunks<H, TH, RS>;
+    constexpr int NCH = Chunks::NCH;                   // 16-byte chunks (4 samples of a row) per thread and half tile
     constexpr int WK = (H / 32) / BK;
-    static_assert(NCH * TH == NR * 4 && NCH >= 2 && (NCH & 1) == 0, "the waves own all tiles, every thread holds G and A chunks");
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     unsigned short *lds = reinterpret_cast<unsigned short *>(lds_raw);
     const int lane = tn::lane_id(), i = lane & 31, h = lane >> 5;
@@ -526,45 +458,21 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_f2_k
         for (int bk = 0; bk < BK; ++bk)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[bn][bk][r] = 0.0f;
-    const int qd = threadIdx.x & 3;
-    int src_off[NCH], dst_off[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const int row = (threadIdx.x + TH * c) >> 2;
-        src_off[c] = (row < H ? row : row - H) * 32 + 4 * qd;          // relative to the tile's G rows (c < NCH / 2) / A rows
-        dst_off[c] = row * RS + 4 * qd;
-    }
+    Chunks ch;
+    ch.init();
     float dbacc[NCH / 2];
 #pragma unroll
     for (int c = 0; c < NCH / 2; ++c) dbacc[c] = 0.0f;
-    const int64_t stride = gridDim.x;
-    typedef const __attribute__((address_space(1))) char gchar;
-    struct Bases { gchar *g, *a; };                                // wave-uniform: the half tile's G rows and A rows
-    auto uniform_global = [](const float *p) {
-        const uint64_t v = (uint64_t)p;
-        const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
-        return (gchar *)u;
-    };
-    auto half_src = [&](int64_t it) {
-        int64_t tile = blockIdx.x + (it >> 1) * stride;
-        tile = tile < n_tiles ? tile : n_tiles - 1;
-        return Bases{uniform_global(stash + (tile * a.rows_total + a.off_g) * 32 + 16 * (it & 1)),
-                     uniform_global(stash + (tile * a.rows_total + a.off_a) * 32 + 16 * (it & 1))};
-    };
-    const int64_t my_tiles = (int64_t)blockIdx.x < n_tiles ? (n_tiles - blockIdx.x + stride - 1) / stride : 0;
-    const int64_t iters = 2 * my_tiles;
+    const int64_t iters = wgrad_half_tiles(n_tiles);
     if (iters == 0) return;
     // two register sets of raw chunks: half tile it + 1 (being converted during half step it) and it + 2 (in flight); a chunk's
     // successor two half tiles on is requested into its own registers as soon as it is converted -- every request has two half
     // steps (~3 us) to land, 64 KB per CU in flight (one set: 32 KB and one half step, which is the loaded HBM latency -- the
     // kernel ran at exactly 32 KB x 256 CUs per half step = 4.9 TB/s)
     f32x4 st[2][NCH];
-    unsigned src_boff[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) src_boff[c] = (unsigned)src_off[c] * 4u;
-    auto load_chunk = [&](const Bases &base, int c, auto set_tag) {
+    auto load_chunk = [&](const HalfBases &base, int c, auto set_tag) {
         constexpr int SET = decltype(set_tag)::value;
-        unsigned off = src_boff[c];
+        unsigned off = ch.src_boff[c];
         asm volatile("" : "+v"(off));
         // (no nt hint here: a half tile takes 64 of a row's 128 bytes and the other half comes out of L2 one half step later -- with
         // the hint the launch takes 0.56 instead of 0.39 ms)
@@ -574,7 +482,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_f2_k
     // writes, 5: bias sum + request of the chunk's successor); G chunks come first (c < NCH / 2)
     unsigned cu[4];
     float cf[2];
-    auto micro = [&](int c, int m, unsigned short *buf, const Bases &nb, auto set_tag) {
+    auto micro = [&](int c, int m, unsigned short *buf, const HalfBases &nb, auto set_tag) {
         constexpr int SET = decltype(set_tag)::value;
         const float sc = c < NCH / 2 ? s_g : s_a;
         if (m < 4) {
@@ -589,7 +497,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_f2_k
                 cu[e + 1] = __builtin_bit_cast(unsigned, ll);
             }
         } else if (m == 4) {
-            unsigned short *d = buf + dst_off[c];
+            unsigned short *d = buf + ch.dst_off[c];
             *reinterpret_cast<uint2 *>(d) = make_uint2(cu[0], cu[2]);
             *reinterpret_cast<uint2 *>(d + PLANE) = make_uint2(cu[1], cu[3]);
         } else {
@@ -600,7 +508,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_f2_k
     using Set0 = std::integral_constant<int, 0>;
     using Set1 = std::integral_constant<int, 1>;
     {
-        const Bases b0 = half_src(0), b1 = half_src(1), b2 = half_src(2 < iters ? 2 : 0);
+        const HalfBases b0 = half_src(a, stash, n_tiles, 0), b1 = half_src(a, stash, n_tiles, 1), b2 = half_src(a, stash, n_tiles, 2 < iters ? 2 : 0);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) load_chunk(b0, c, Set0{});
 #pragma unroll
@@ -613,10 +521,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_f2_k
     }
     __syncthreads();
     int g_off[BN], a_off[BK];
-#pragma unroll
-    for (int bn = 0; bn < BN; ++bn) g_off[bn] = (32 * (tn0 + bn) + i) * RS + 8 * h;
-#pragma unroll
-    for (int bk = 0; bk < BK; ++bk) a_off[bk] = (H + 32 * (tk0 + bk) + i) * RS + 8 * h;
+    wgrad_operand_offsets<H, RS>(tn0, tk0, i, h, g_off, a_off);
     auto read_op = [&](const unsigned short *buf, int off) {
         Op2 o;
         o.hi = *reinterpret_cast<const u32x4 *>(buf + off);
@@ -631,7 +536,7 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_f2_k
         using SetN = std::integral_constant<int, P ^ 1>;
         const unsigned short *bc = lds + P * BUF;
         unsigned short *bnx = lds + (P ^ 1) * BUF;
-        const Bases nb = half_src(it + 3 < iters ? it + 3 : it + 1 < iters ? it + 1 : it);
+        const HalfBases nb = half_src(a, stash, n_tiles, it + 3 < iters ? it + 3 : it + 1 < iters ? it + 1 : it);
         Op2 gop[BN];
 #pragma unroll
         for (int bn = 0; bn < BN; ++bn) gop[bn] = read_op(bc, g_off[bn]);
@@ -675,41 +580,9 @@ __global__ __launch_bounds__(64 * (H / 32 / BN) * (H / 32 / BK)) void wgrad_f2_k
     half_step(iters - 2, Set0{}, std::true_type{});
     half_step(iters - 1, Set1{}, std::false_type{});
     asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-    const float c_out = inv_g * inv_a;
-#pragma unroll
-    for (int bn = 0; bn < BN; ++bn)
-#pragma unroll
-        for (int bk = 0; bk < BK; ++bk) {
-            const int k = 32 * (tk0 + bk) + i;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int nn = 32 * (tn0 + bn) + frow(r, h);
-                atomicAdd(&a.gW[(int64_t)nn * a.K + k], acc[bn][bk][r] * c_out);
-            }
-        }
-#pragma unroll
-    for (int c = 0; c < NCH / 2; ++c) {
-        float sgm = dbacc[c];
-        sgm += __shfl_xor(sgm, 1, 64);
-        sgm += __shfl_xor(sgm, 2, 64);
-        const int row = (threadIdx.x + TH * c) >> 2;
-        if (qd == 0) atomicAdd(&a.gB[row], sgm);
-    }
+    flush_tiles<false>(a, tn0, tk0, i, h, acc, inv_g * inv_a);
+    flush_bias<TH>(a.gB, dbacc);
 }
-
-template <int H, int BN, int BK>
-int launch_wgrad(const WgradArgs &w, int64_t n, const float *stash, hipStream_t s)
-{
-    constexpr size_t lds_bytes = (size_t)2 * 2 * (2 * H) * 24 * 2;
-    auto kern = wgrad_f2_kernel<H, BN, BK>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd(f16x2): cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int per_cu = lds_bytes * 2 <= (size_t)LDS_LIMIT_BYTES ? 2 : 1;
-    kern<<<dim3((unsigned)std::min<int64_t>(n_tiles, 256 * per_cu)), dim3(64 * (H / 32 / BN) * (H / 32 / BK)), lds_bytes, s>>>(w, n, stash);
-    return tn::check_launch("wgrad_f2_kernel");
-}
-
 
 // ------------------------------------------------------------------------------------------------
 // First layer of a wide stack (<= 64 encoded or plain inputs as workspace rows, enc_rows_kernel) in the f16x2 arithmetic: the
@@ -803,48 +676,6 @@ __global__ __launch_bounds__(WPB * 64) void fwd_first_f2_kernel(FwdLayerArgs a, 
     }
 }
 
-template <int H>
-int launch_first(const FwdLayerArgs &f, int64_t n, float *stash, hipStream_t s)
-{
-    constexpr int WPB = 8;
-    constexpr size_t lds_bytes = (size_t)2 * H * 72 * 2 + H * 4 + 64;
-    auto kern = fwd_first_f2_kernel<H, WPB>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_fwd(f16x2, first layer): cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int per_cu = (int)std::min<size_t>(4, (size_t)LDS_LIMIT_BYTES / lds_bytes);
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + WPB - 1) / WPB, 256 * per_cu));
-    kern<<<dim3((unsigned)bl), dim3(WPB * 64), lds_bytes, s>>>(f, n, stash);
-    return tn::check_launch("fwd_first_f2_kernel");
-}
-
-template <int H, bool LAST>
-int launch_fwd(const FwdLayerArgs &f, int64_t n, float *stash, float *y, hipStream_t s)
-{
-    using G = F2Geom<H>;
-    auto kern = fwd_f2_kernel<H, LAST>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_fwd(f16x2): cannot reserve %zu B of LDS: %s", G::lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + G::STREAMS - 1) / G::STREAMS, 256));
-    kern<<<dim3((unsigned)bl), dim3(G::THREADS), G::lds_bytes, s>>>(f, n, stash, y);
-    return tn::check_launch("fwd_f2_kernel");
-}
-
-template <int H>
-int launch_dgrad(const DgradArgs &d, int64_t n, float *stash, hipStream_t s)
-{
-    using G = F2Geom<H>;
-    if (d.off_bits < 0) return tn::fail(TN_E_CONFIG, "mlp_bwd(f16x2): the data gradient takes its ReLU masks as bit rows");
-    auto kern = dgrad_f2_kernel<H>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd(f16x2): cannot reserve %zu B of LDS: %s", G::lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + G::STREAMS - 1) / G::STREAMS, 256));
-    kern<<<dim3((unsigned)bl), dim3(G::THREADS), G::lds_bytes, s>>>(d, n, stash);
-    return tn::check_launch("dgrad_f2_kernel");
-}
-
 }  // namespace
 
 namespace tn {
@@ -852,33 +683,45 @@ namespace layers {
 
 __attribute__((visibility("hidden"))) int launch_fwd_f2(int H, bool last, const FwdLayerArgs &f, int64_t n, float *stash, float *y, hipStream_t s)
 {
-    if (H == 256) return last ? launch_fwd<256, true>(f, n, stash, y, s) : launch_fwd<256, false>(f, n, stash, y, s);
-    if (H == 128) return last ? launch_fwd<128, true>(f, n, stash, y, s) : launch_fwd<128, false>(f, n, stash, y, s);
-    return tn::fail(TN_E_CONFIG, "mlp_fwd(f16x2): width 128 or 256");
+    return for_width(H, "mlp_fwd(f16x2): width 128 or 256", [&](auto width) {
+        using G = F2Geom<decltype(width)::value>;
+        auto kern = last ? fwd_f2_kernel<decltype(width)::value, true> : fwd_f2_kernel<decltype(width)::value, false>;
+        return launch(kern, G::THREADS / 64, G::lds_bytes, stream_blocks(n, G::STREAMS), s, "mlp_fwd(f16x2): fwd_f2_kernel", f, n, stash, y);
+    });
 }
 
 // first layer (K <= 64 input rows, hidden output: ReLU, rows + bit rows)
 __attribute__((visibility("hidden"))) int launch_fwd_first_f2(int H, const FwdLayerArgs &f, int64_t n, float *stash, hipStream_t s)
 {
     if (f.Kp > 64 || f.K > 64 || f.N > H) return tn::fail(TN_E_CONFIG, "mlp_fwd(f16x2, first layer): at most 64 input rows");
-    if (H == 256) return launch_first<256>(f, n, stash, s);
-    if (H == 128) return launch_first<128>(f, n, stash, s);
-    return tn::fail(TN_E_CONFIG, "mlp_fwd(f16x2): width 128 or 256");
+    return for_width(H, "mlp_fwd(f16x2): width 128 or 256", [&](auto width) {
+        constexpr int W = decltype(width)::value, WPB = 8;
+        constexpr size_t lds_bytes = (size_t)2 * W * 72 * 2 + W * 4 + 64;
+        return launch(fwd_first_f2_kernel<W, WPB>, WPB, lds_bytes, grid_per_cu(n, WPB, lds_bytes), s, "mlp_fwd(f16x2, first layer): fwd_first_f2_kernel",
+                      f, n, stash);
+    });
 }
 
 __attribute__((visibility("hidden"))) int launch_dgrad_f2(int H, const DgradArgs &d, int64_t n, float *stash, hipStream_t s)
 {
-    if (H == 256) return launch_dgrad<256>(d, n, stash, s);
-    if (H == 128) return launch_dgrad<128>(d, n, stash, s);
-    return tn::fail(TN_E_CONFIG, "mlp_bwd(f16x2): width 128 or 256");
+    if (d.off_bits < 0) return tn::fail(TN_E_CONFIG, "mlp_bwd(f16x2): the data gradient takes its ReLU masks as bit rows");
+    return for_width(H, "mlp_bwd(f16x2): width 128 or 256", [&](auto width) {
+        using G = F2Geom<decltype(width)::value>;
+        return launch(dgrad_f2_kernel<decltype(width)::value>, G::THREADS / 64, G::lds_bytes, stream_blocks(n, G::STREAMS), s,
+                      "mlp_bwd(f16x2): dgrad_f2_kernel", d, n, stash);
+    });
 }
 
 __attribute__((visibility("hidden"))) int launch_wgrad_f2(int H, const WgradArgs &w, int64_t n, const float *stash, hipStream_t s)
 {
     if (w.first || w.N != H || w.K != H || !w.g_max || !w.a_max) return tn::fail(TN_E_CONFIG, "mlp_bwd(f16x2): square hidden layers with both maxima");
-    if (H == 256) return launch_wgrad<256, 4, 2>(w, n, stash, s);
-    if (H == 128) return launch_wgrad<128, 2, 2>(w, n, stash, s);
-    return tn::fail(TN_E_CONFIG, "mlp_bwd(f16x2): width 128 or 256");
+    return for_width(H, "mlp_bwd(f16x2): width 128 or 256", [&](auto width) {
+        constexpr int W = decltype(width)::value, BN = W == 256 ? 4 : 2, BK = 2;
+        constexpr size_t lds_bytes = (size_t)2 * 2 * (2 * W) * 24 * 2;
+        const int per_cu = lds_bytes * 2 <= (size_t)LDS_LIMIT_BYTES ? 2 : 1;
+        return launch(wgrad_f2_kernel<W, BN, BK>, (W / 32 / BN) * (W / 32 / BK), lds_bytes, grid_blocks(n, 1, 256 * per_cu), s,
+                      "mlp_bwd(f16x2): wgrad_f2_kernel", w, n, stash);
+    });
 }
 
 }  // namespace layers

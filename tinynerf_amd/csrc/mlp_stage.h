@@ -157,6 +157,14 @@ __device__ __forceinline__ void load_rows(const float *__restrict__ rows, f32x16
         t[r] = *reinterpret_cast<const __attribute__((address_space(1))) float *>(base + off + (unsigned)(((r & 3) + 8 * (r >> 2)) * 128));
 }
 
+// global_load_lds_dwordx4: 16 bytes per lane from `src` (per lane) to LDS at `dst` (wave-uniform) + 16 * lane; counted in vmcnt.
+// NT: non-temporal hint (aux bit 1).  (Kept in a __device__ function: the builtin inside a __global__ template makes hipcc's host
+// pass drop the kernel's stub.)
+template <bool NT = false>
+__device__ __forceinline__ void glds16(const float *src, float *dst) {
+    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, NT ? 2 : 0);
+}
+
 // Bit r = (t[r] > 0) for ReLU outputs (t >= 0, so "> 0" is "bit pattern != 0"; -0.0 cannot occur after fmaxf(x, 0)
 // ... it can: fmaxf(-0.0, 0) may return either zero, hence the shift that drops the sign bit).  Two VALU operations per
 // element (min, shift-or) instead of compare + select + or: VALU instructions are what the MFMA-heavy kernels run out of.
@@ -232,14 +240,19 @@ inline int64_t grid_per_cu(int64_t n, int waves, size_t lds) {
 
 // the one way a planned kernel is launched: reserve its dynamic LDS (if any), launch, check
 template <class... P, class... A>
-int launch(void (*kern)(P...), int waves, size_t lds, int64_t blocks, hipStream_t s, const char *what, A... args)
+int launch(void (*kern)(P...), int waves, size_t lds, dim3 grid, hipStream_t s, const char *what, A... args)
 {
     if (lds) {
         const hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) { tn::set_error("%s: cannot reserve %zu B of LDS: %s", what, lds, hipGetErrorString(e)); return (int)e; }
     }
-    kern<<<dim3((unsigned)blocks), dim3(waves * 64), lds, s>>>(args...);
+    kern<<<grid, dim3(waves * 64), lds, s>>>(args...);
     return tn::check_launch(what);
+}
+template <class... P, class... A>
+int launch(void (*kern)(P...), int waves, size_t lds, int64_t blocks, hipStream_t s, const char *what, A... args)
+{
+    return launch(kern, waves, lds, dim3((unsigned)blocks), s, what, args...);
 }
 
 inline int plan(const tn_mlp_desc *d, MlpArgs &a, int &H)

@@ -23,6 +23,8 @@ namespace {
 
 using tn::f32x16;
 using tn::f32x4;
+using tn::frow;
+using tn::mlp::glds16;
 
 struct WgradRowsArgs {
     const float *g_rows;        // G_0 rows of tile t at g_rows + t * g_stride   ([NG][32] floats)
@@ -38,12 +40,6 @@ struct WgradRowsArgs {
     float *gW2 = nullptr, *gB2 = nullptr;
     int ldw2 = 0, col02 = 0;
 };
-
-__device__ __forceinline__ int frow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-__device__ __forceinline__ void glds16(const float *src, float *dst) {
-    __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void *)dst, 16, 0, 0);
-}
 
 // B3: the products as exact bf16 triplets (b3_device.h: six 32 x 32 x 16 MFMAs per 16 samples instead of eight 32 x 32 x 2 fp32 ones per
 // 16 -- 2.7 x less matrix time, results equal to fp32 rounding): the two-head form owns four tiles per wave and is matrix-bound on the fp32
@@ -188,13 +184,8 @@ template <int NG, int NA, int BN, int BK, bool B3 = false>
 int launch_rows(const WgradRowsArgs &w, int64_t n, hipStream_t s)
 {
     constexpr size_t lds_bytes = (size_t)2 * (NG + NA) * 32 * sizeof(float);
-    auto kern = wgrad_rows_kernel<NG, NA, BN, BK, B3>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd: cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
     const int per_cu = lds_bytes * 2 <= (size_t)tn::mlp::LDS_LIMIT_BYTES ? 2 : 1;
-    kern<<<dim3((unsigned)std::min<int64_t>(n_tiles, 256 * per_cu)), dim3(512), lds_bytes, s>>>(w, n);
-    return tn::check_launch("wgrad_rows_kernel");
+    return tn::mlp::launch(wgrad_rows_kernel<NG, NA, BN, BK, B3>, 8, lds_bytes, tn::mlp::grid_blocks(n, 1, 256 * per_cu), s, "mlp_bwd: wgrad_rows_kernel", w, n);
 }
 
 }  // namespace
