@@ -646,6 +646,35 @@ typedef struct tn_camera_table {
 enum { TN_LENS_PINHOLE = 0, TN_LENS_OPENCV = 1, TN_LENS_FISHEYE = 2 };
 int tn_camera_rays(const tn_camera_table *cams, const int32_t *idx, int64_t first, int64_t stride, int64_t n,
                    float *out_o, float *out_d, float *out_rgb, void *stream);
+/* Coloured point cloud of rendered rays: filter, back-projection and order-preserving compaction of per-ray maps (tn_ray_maps'
+ * opacity and depth, the composited colour), all on the device.  fp32 throughout, every fused multiply-add an explicit fmaf:
+ *   point   p_c = fmaf(depth_i, d_ic, o_ic), c = x, y, z; d is used as given (the harness' rays are unit length: depth is a distance)
+ *   ray i is kept when  opacity_i >= min_opacity (false for NaN)  and  depth_i > 0 and finite  and  all three p_c finite  and --
+ *           with a box -- lo_c <= p_c <= hi_c on every axis, faces inclusive
+ *   colour  the expected colour given a hit, the background taken out again:
+ *           u_c = fmaf(-(1 - opacity_i), bg_c, rgb_ic) / opacity_i  (correctly rounded division), c = min(max(u_c, 0), 1) with
+ *           NaN -> 0, byte = (uint8_t)fmaf(c, 255.0f, 0.5f); bg == NULL is bg = (0, 0, 0), bit for bit
+ * Output order is ray order: the k-th kept ray writes row k of points, colors and src (src = its ray index).  *count = the number
+ * of kept rays whatever `capacity` is; rows k >= capacity are not written and no row at or beyond min(count, capacity) is touched;
+ * with capacity == 0 the three output pointers may be NULL (count only).  Three launches on `stream` (per-wave ballots, one
+ * workgroup scanning the workgroup counts, ranked stores), no atomics: the same bytes on every call.  `workspace`:
+ * tn_points_workspace_bytes(n) bytes, 8-byte aligned like `count` (TN_E_ALIGN otherwise); contents undefined afterwards.
+ * Checked before any launch: TN_E_SIZE for n < 0, capacity < 0 or n >= 2^31 (src is int32); TN_E_CONFIG unless min_opacity > 0
+ * (NaN included: the division stays defined); TN_E_NULL for a null required pointer (bg and box are optional; the inputs and the
+ * workspace are not read for n == 0).  n == 0 writes *count = 0 and returns TN_OK.  No reference call site: the reference renders
+ * images and exports no geometry. */
+int tn_points_workspace_bytes(int64_t n, int64_t *bytes);                       /* host only */
+int tn_points_compact(const float *rays_o, const float *rays_d,                 /* [n,3] each */
+                      const float *rgb,                                         /* [n,3] composited colour */
+                      const float *opacity, const float *depth,                 /* [n] */
+                      const float *bg,                                          /* [3] or NULL (= 0,0,0) */
+                      const float *box,                                         /* [6] lo xyz, hi xyz, device; NULL = no crop */
+                      float min_opacity, int64_t n, int64_t capacity,
+                      float *points,                                            /* [capacity,3] */
+                      uint8_t *colors,                                          /* [capacity,3] */
+                      int32_t *src,                                             /* [capacity] ray index of each point */
+                      int64_t *count,                                           /* device, 1 value */
+                      void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * optimizer step of the harness                       (reference run.py:186,258-260: torch.optim.Adam)

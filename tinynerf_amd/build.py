@@ -35,6 +35,7 @@ SOURCES = {
     "planes_reg.hip": FAST,
     "metrics.hip": FAST,
     "cameras.hip": FAST,
+    "points.hip": FAST,
     "kplanes.hip": FAST + ["-munsafe-fp-atomics"],
     "cobafa.hip": STRICT + ["-munsafe-fp-atomics"],   # sawtooth warp x (res-1): an fma in f*x - floor moves taps
     "hashgrid.hip": FAST + ["-munsafe-fp-atomics"],

@@ -930,11 +930,14 @@ def evaluate(dataset, rendered: List[torch.Tensor], indices: List[int], ssim: bo
 
 def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=None, eval_every: Optional[int] = None,
           eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
-          render_maps: bool = False, ssim: bool = False):
+          render_maps: bool = False, ssim: bool = False, pointcloud: int = 0, pointcloud_crop=None):
     """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device, or a data.CameraRaysDataset (a
     photographed scene: the trainer makes its rays from the camera table, ``Trainer(ray_source=...)``).  ``render_maps``: the final
     test render also writes the depth / opacity maps of every image (``infer(maps=True)``).  ``ssim``: the periodic evaluation and
-    the final test render also compute each image's SSIM (``evaluate(ssim=True)``; ``metrics_eval.json`` / ``metrics_test.json``)."""
+    the final test render also compute each image's SSIM (``evaluate(ssim=True)``; ``metrics_eval.json`` / ``metrics_test.json``).
+    ``pointcloud`` > 0 (with `test_set` and `output`): after the final test render the test views' surface points, at most that
+    many, go to ``pointcloud.ply`` (``points.export_pointcloud``; ``pointcloud_crop``: its ``crop``); with ``render_maps``
+    the maps of that render are used, so every view is rendered once.  At 0 nothing of it is imported, allocated or launched."""
     import json
     from dataclasses import asdict
     from .data import CameraRaysDataset
@@ -965,6 +968,10 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
     if test_set is not None:
         idx = list(range(len(test_set)))
         rendered = infer(tr, test_set, idx, output, "test_full", maps=render_maps)
+        if pointcloud > 0 and output is not None:
+            from .points import export_pointcloud
+            export_pointcloud(tr, test_set, idx, output / "pointcloud.ply", n_points=pointcloud, crop=pointcloud_crop, seed=cfg.seed,
+                              rendered=rendered if render_maps else None)
         if render_maps:
             rendered = [r["rgb"] for r in rendered]
         if test_set.rgbs:

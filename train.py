@@ -13,7 +13,7 @@ import uuid
 from pathlib import Path
 
 # (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight, --ssim,
-# --downscale and --holdout_every
+# --downscale, --holdout_every, --export_pointcloud and --pointcloud_crop
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -31,6 +31,9 @@ FLAGS = (
     ("--ssim", dict(action="store_true", help="metrics_eval.json / metrics_test.json also carry each image's SSIM (else 0.0)")),
     ("--downscale", dict(type=int, default=1, help="nerfstudio: load the images N times smaller (images_N/ if present, else box-filtered)")),
     ("--holdout_every", dict(type=int, default=8, help="nerfstudio captures without split lists: every N-th frame is val / test")),
+    ("--export_pointcloud", dict(type=int, default=0, metavar="N", help="write pointcloud.ply: at most N coloured surface points of the test views (0: off)")),
+    ("--pointcloud_crop", dict(type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                               help="box the exported points must lie in (default: the box the marcher samples uniformly)")),
 )
 
 
@@ -93,7 +96,8 @@ def main(argv=None):
     print(f"Experiment saved to {run_dir}")
     cfg = TrainConfig(method=args.method, scene_type=args.scene_type, batch_size=args.batch_size, n_samples=args.n_samples, seed=seed,
                       distortion_weight=args.distortion_weight)
-    train(cfg, train_rays, eval_set, test_set, run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim)
+    train(cfg, train_rays, eval_set, test_set, run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim,
+          pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop)
 
 
 if __name__ == "__main__":
