@@ -308,6 +308,8 @@ def compare(got: Dict[str, np.ndarray], ref: Dict, keys: Sequence[str] = ("y", "
 # mlp_b3_layers.hip, mlp_wgrad_rows.hip).
 PART_A = {
     "mlp40_64x2_3":      (Spec("none", 40, 0, 64, 1, 3, "none"), "heads"),
+    "mlp40_64x1_3":      (Spec("none", 40, 0, 64, 0, 3, "none"), "heads"),          # two-pass backward with a partial second k tile / column block
+    "mlp38_64x2_6":      (Spec("none", 38, 0, 64, 1, 6, "none"), "heads"),          # in_dim % 4 != 0, six outputs: generic first layer, MFMA output layer
     "sigma96_64x1_1":    (Spec("none", 96, 0, 64, 0, 1, "exp_m1"), "heads"),        # VanillaOpacityDecoder(96)
     "sigma96_64x2_1":    (Spec("none", 96, 0, 64, 1, 1, "exp_m1"), "heads"),
     "color99_64x2_3":    (Spec("dircat", 48, 8, 64, 1, 3, "sigmoid"), "heads"),     # VanillaColorDecoder(8, 48, 64, 1)

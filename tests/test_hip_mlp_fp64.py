@@ -38,6 +38,14 @@ over all shapes, sizes, stash on / off and both forms -- width 64: f16x2 y 0.002
 The layer-wise and the cross-layer forms, and stash on and off, give the same figures to three digits.  mlp36_128x2_37 (an output below the
 width that is no multiple of 4: the element-wise y stores of the last layer's narrow epilogue, emit_last_narrow in mlp_layers.h, and a second
 output block with five rows) stays below them: y 0.001, grad_x 0.003, dW 0.046, db 0.041 over the three modes.
+Two shapes reach the edges of the width-64 kernels that the reference's decoders do not.  mlp40_64x1_3 (two layers: the two-pass backward,
+stash on and off; in_dim 40, three outputs) runs mlp_wgrad_kernel<64, 1, 1, 8, 4> with a partial second k tile in its flush (k < K), the
+chain's grad_x store with a partial second 32-column block, the <= 4-output layer with out = 3 and first_dgrad on the main head: f16x2 y
+0.005, grad_x 0.041, dW 0.081, db 0.062; fp32 0.006, 0.052, 0.243, 0.124 (the largest dW and db shares are those of n = 1, one term per
+sum).  mlp38_64x2_6 (in_dim % 4 != 0, six outputs) takes the generic first layer with the element-wise tail of fetch_input and the MFMA
+output layer with element-wise y stores wherever tn_mlp_fwd runs it (mlp_fwd_kernel<64, true, 16, false, false, false>, under f16x2 as
+well: the f16x2 heads need in_dim % 16 == 0); with three layers its stashed forward and its backward are the layer-by-layer form: f16x2
+y 0.001, grad_x 0.008, dW 0.023, db 0.057; fp32 0.001, 0.011, 0.029, 0.098.
 """
 import ctypes as C
 

@@ -16,25 +16,14 @@
 #include "mlp_stage.h"
 #include "mlp_f2_heads.h"
 #include "kplanes_device.h"
+#include "phase_timers.h"
 #include <algorithm>
 
-#ifdef TN_PHASE_TIMERS
-__device__ unsigned long long tn_phase_cycles[16];
-#define TN_PT_BEGIN unsigned long long pt_ = __builtin_amdgcn_s_memtime();
-#define TN_PTG_BEGIN unsigned long long ptg_ = __builtin_amdgcn_s_memtime();
-#define TN_PTG(k) { __builtin_amdgcn_sched_barrier(0); const unsigned long long n_ = __builtin_amdgcn_s_memtime(); if (lane == 0) atomicAdd(&tn_phase_cycles[k], n_ - ptg_); ptg_ = n_; }
-#define TN_PT(k) { __builtin_amdgcn_sched_barrier(0); const unsigned long long n_ = __builtin_amdgcn_s_memtime(); if (lane == 0) atomicAdd(&tn_phase_cycles[k], n_ - pt_); pt_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-extern "C" int tn_debug_phase_cycles(unsigned long long *out, int reset) {
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(tn_phase_cycles), sizeof(unsigned long long) * 16);
-    if (reset) { unsigned long long z[16] = {}; hipMemcpyToSymbol(HIP_SYMBOL(tn_phase_cycles), z, sizeof(z)); }
-    return 0;
-}
-#else
-#define TN_PT_BEGIN
-#define TN_PT(k)
-#define TN_PTG_BEGIN
-#define TN_PTG(k)
-#endif
+TN_PHASE_COUNTERS(tn_phase_cycles, tn_debug_phase_cycles)                  // (scripts/phase_time.py)
+#define TN_PT_BEGIN TN_PHASE_BEGIN(pt_)
+#define TN_PT(k) TN_PHASE(tn_phase_cycles, pt_, k)
+#define TN_PTG_BEGIN TN_PHASE_BEGIN(ptg_)
+#define TN_PTG(k) TN_PHASE_RUNNING(tn_phase_cycles, ptg_, k)
 namespace {
 
 using tn::f32x16;
@@ -159,10 +148,7 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
           float s_x;
           f2_scales(f2_xmax(m), s_x, inv_x);
 #pragma unroll
-          for (int b = 0; b < 6; ++b) {
-              const float v[8] = {fr[2 * b][0], fr[2 * b][1], fr[2 * b][2], fr[2 * b][3], fr[2 * b + 1][0], fr[2 * b + 1][1], fr[2 * b + 1][2], fr[2 * b + 1][3]};
-              f2_split8(v, s_x, xbh[b], xbl[b]);
-          }
+          for (int b = 0; b < 6; ++b) f2_split8(fr[2 * b], fr[2 * b + 1], s_x, xbh[b], xbl[b]);
       }
       TN_PTG(8)
       auto head2 = [&](const MlpArgs &a, const float *ldsw, const float *__restrict__ aux, float *__restrict__ y,
@@ -174,26 +160,15 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
         const int64_t row = tile * 32 + j;
         const bool valid = row < n;
         if constexpr (!STASH) {
-            if (a.row_gate != nullptr) {
-                const float gate = valid ? a.row_gate[row] : 0.0f;
-                if (!__any(gate != 0.0f)) {
-                    if (valid && h == 0) {
-                        for (int o = 0; o < a.out_dim; ++o) {
-                            y[row * a.out_dim + o] = 0.0f;
-                            if (pre_act) pre_act[row * a.out_dim + o] = 0.0f;
-                        }
-                    }
-                    return;
-                }
-            }
+            if (gate_skips_tile(a, row, valid, h, y, pre_act)) return;
         }
         float *stH = nullptr, *stQ = nullptr;
         unsigned *stM = nullptr;
         if constexpr (STASH) {
-            const int NH = L - 1;
-            stH = stash + tile * (int64_t)(stash_rows(H, NH, 0) * 32);
-            stQ = stH + stash_rows_w(H, NH, 0) * 32;
-            stM = reinterpret_cast<unsigned *>(stQ + 4 * 32);
+            const StashTile st(H, L - 1, 0);
+            stH = stash + tile * (int64_t)st.floats();
+            stQ = stH + st.pre();
+            stM = reinterpret_cast<unsigned *>(stH + st.masks());
         }
         const float *scl = ldsw + a.f2_scale;
         TN_PT_BEGIN
@@ -201,6 +176,9 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
         const _Float16 *W0 = reinterpret_cast<const _Float16 *>(ldsw + a.w_off[0]);
         const int plane0 = a.f2_plane[0], st0 = a.stride[0];
         const int nbx = a.in_dim >> 4;
+        // (This loop stays spelt out: through tn::zero_tiles the lean K-Planes training forward converts its activations with another mix
+        // of VALU instructions.  For the same reason this head keeps its own output layer, the 8-value maximum of the two-pass first layer
+        // below and the 48-value maximum of the K-Planes features above, where the fp32 head or tn::max_abs4 would serve: LABNOTES 9.11.)
         f32x16 acc[T];
 #pragma unroll
         for (int ob = 0; ob < T; ++ob)
@@ -239,13 +217,12 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
                 }
                 float m = 0.0f;
 #pragma unroll
-                for (int e = 0; e < 2 * XB; ++e) m = fmaxf(fmaxf(m, fmaxf(fabsf(xv[e][0]), fabsf(xv[e][1]))), fmaxf(fabsf(xv[e][2]), fabsf(xv[e][3])));
+                for (int e = 0; e < 2 * XB; ++e) m = tn::max_abs4(m, xv[e]);
                 f2_scales(f2_xmax(m), s_x, inv0);
 #pragma unroll
                 for (int b = 0; b < XB; ++b) {
-                    const float v[8] = {xv[2 * b][0], xv[2 * b][1], xv[2 * b][2], xv[2 * b][3], xv[2 * b + 1][0], xv[2 * b + 1][1], xv[2 * b + 1][2], xv[2 * b + 1][3]};
                     u32x4h bh, bl;
-                    f2_split8(v, s_x, bh, bl);
+                    f2_split8(xv[2 * b], xv[2 * b + 1], s_x, bh, bl);
                     f2_block(W0, plane0, st0, j, h, b, bh, bl, acc);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -261,9 +238,8 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
             for (int b = 0; b < nbx; ++b) {
                 const int bn = b + 1 < nbx ? b + 1 : b;
                 const f32x4 n0 = *reinterpret_cast<const f32x4 *>(xr + 16 * bn), n1 = *reinterpret_cast<const f32x4 *>(xr + 16 * bn + 8);
-                const float v[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
                 u32x4h bh, bl;
-                f2_split8(v, s_x, bh, bl);
+                f2_split8(c0, c1, s_x, bh, bl);
                 f2_block(W0, plane0, st0, j, h, b, bh, bl, acc);
                 __builtin_amdgcn_sched_barrier(0);
                 c0 = n0; c1 = n1;
@@ -291,21 +267,17 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
             for (int g = 0; g < 8; ++g) {                    // (groups past the table repeat the last one: their weights are zero)
                 if (PREF && prefetched) av[g] = avp[PREF ? g : 0];
                 else av[g] = *reinterpret_cast<const f32x4 *>(arow + 8 * (g < nga ? g : nga - 1));
-                m = fmaxf(fmaxf(m, fmaxf(fabsf(av[g][0]), fabsf(av[g][1]))), fmaxf(fabsf(av[g][2]), fabsf(av[g][3])));
+                m = tn::max_abs4(m, av[g]);
             }
             float s_a, inv_a;
             f2_scales(f2_xmax(m), s_a, inv_a);
-#pragma unroll
-            for (int ob = 0; ob < T; ++ob)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[ob][r] = 0.0f;
+            tn::zero_tiles(acc);
             const int nba = (a.K0_pad - a.in_dim + 15) >> 4;
 #pragma unroll
             for (int ba = 0; ba < 4; ++ba) {
                 if (ba < nba) {
-                    const float v[8] = {av[2 * ba][0], av[2 * ba][1], av[2 * ba][2], av[2 * ba][3], av[2 * ba + 1][0], av[2 * ba + 1][1], av[2 * ba + 1][2], av[2 * ba + 1][3]};
                     u32x4h bh, bl;
-                    f2_split8(v, s_a, bh, bl);
+                    f2_split8(av[2 * ba], av[2 * ba + 1], s_a, bh, bl);
                     f2_block(W0, plane0, st0, j, h, nbx + ba, bh, bl, acc);
                     __builtin_amdgcn_sched_barrier(0);
                 }
@@ -324,7 +296,7 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
 #pragma unroll
             for (int r = 0; r < 16; ++r) act[ob][r] += bias[r];
             act[ob] = tn::relu16(act[ob]);
-            if constexpr (STASH) { stM[ob * 64 + lane] = relu_bits(act[ob]); if constexpr (!LEAN) store_rows(stH, act[ob], ob, j, h); }
+            if constexpr (STASH) keep_relu<!LEAN>(act[ob], stM[ob * 64 + lane], stH, ob, j, h);      // (TN_MLP_LEAN leaves the H rows out)
         }
         TN_PT(3)
         // ---- hidden layers ----
@@ -333,10 +305,7 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
             TN_PT(4)
             if constexpr (STASH) {
 #pragma unroll
-                for (int ob = 0; ob < T; ++ob) {
-                    stM[(l * T + ob) * 64 + lane] = relu_bits(act[ob]);
-                    if constexpr (!LEAN) store_rows(stH + l * H * 32, act[ob], ob, j, h);       // (TN_MLP_LEAN leaves the H rows out)
-                }
+                for (int ob = 0; ob < T; ++ob) keep_relu<!LEAN>(act[ob], stM[(l * T + ob) * 64 + lane], stH + l * H * 32, ob, j, h);
             }
         }
         TN_PT(5)
@@ -373,27 +342,9 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
         const int64_t row = tile * 32 + j;
         const bool valid = row < n;
         if constexpr (!STASH) {
-            if (a.row_gate != nullptr) {                    // inference: nothing downstream sees rows whose gate is 0
-                const float gate = valid ? a.row_gate[row] : 0.0f;
-                if (!__any(gate != 0.0f)) {
-                    if (valid && h == 0) {
-                        for (int o = 0; o < a.out_dim; ++o) {
-                            y[row * a.out_dim + o] = 0.0f;
-                            if (pre_act) pre_act[row * a.out_dim + o] = 0.0f;
-                        }
-                    }
-                    return;
-                }
-            }
+            if (gate_skips_tile(a, row, valid, h, y, pre_act)) return;
         }
         const float *xrow = KP ? nullptr : x + (valid ? row : 0) * a.in_dim;
-        float aux3[3] = {0.f, 0.f, 0.f};
-        const float *auxrow = nullptr;
-        if (!FAST && valid) {
-            if (a.enc == TN_ENC_POSENC) { aux3[0] = xrow[0]; aux3[1] = xrow[1]; aux3[2] = xrow[2]; }
-            else if (a.enc == TN_ENC_DIR_CAT) { aux3[0] = aux[3 * row]; aux3[1] = aux[3 * row + 1]; aux3[2] = aux[3 * row + 2]; }
-            else if (a.enc == TN_ENC_AUX_CAT) auxrow = aux + (int64_t)(a.aux_index ? a.aux_index[row] : row) * a.aux_stride;
-        }
         float *stH = nullptr, *stE = nullptr, *stQ = nullptr;
         unsigned *stM = nullptr;
         int xs = 0, extra = 0;
@@ -401,10 +352,11 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
             const int NH = L - 1;
             extra = extra_rows(a.enc, a.in_dim, a.K0_pad);
             xs = x_slots(a.enc, a.in_dim);
-            stH = stash + tile * (int64_t)(stash_rows(H, NH, extra) * 32);
-            stE = stH + (2 * NH * H + 4) * 32;
-            stQ = stH + stash_rows_w(H, NH, extra) * 32;
-            stM = reinterpret_cast<unsigned *>(stQ + 4 * 32);
+            const StashTile st(H, NH, extra);
+            stH = stash + tile * (int64_t)st.floats();
+            stE = stH + st.e();
+            stQ = stH + st.pre();
+            stM = reinterpret_cast<unsigned *>(stH + st.masks());
         }
         // ---- layer 0: inputs streamed 4 slots at a time, prefetched one group ahead ----
         const float *W0 = WLDS ? ldsw + a.w_off[0] : a.W[0];
@@ -468,44 +420,16 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
                 for (int ob = 0; ob < T; ++ob) w[ob] = wn[ob];
             }
         } else {
-        f32x4 b = fetch_input(a, xrow, aux3, valid, 0, h, auxrow);
-        for (int g = 0; g < G0; ++g) {
-            f32x4 bn = {0.f, 0.f, 0.f, 0.f};
-            if (g + 1 < G0) bn = fetch_input(a, xrow, aux3, valid, g + 1, h, auxrow);
-            f32x4 w[T];
-#pragma unroll
-            for (int ob = 0; ob < T; ++ob) {
-                if constexpr (WLDS) w[ob] = load_a4<true>(W0, 32 * ob + j, 8 * g + 4 * h, a.K0, a.stride[0]);
-                else if (a.enc != TN_ENC_DIR_CAT && a.enc != TN_ENC_AUX_CAT) w[ob] = load_a4<false>(W0, 32 * ob + j, 8 * g + 4 * h, a.K0, a.K0);
-                else {   // global first layer of a dir_cat head: slot -> torch column, one dword at a time
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int q = 8 * g + 4 * h + u;
-                        w[ob][u] = q < a.K0 ? W0[(int64_t)(32 * ob + j) * a.K0 + layer0_col(a, q)] : 0.0f;
-                    }
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int ob = 0; ob < T; ++ob) act[ob] = tn::mfma32(w[ob][u], b[u], act[ob]);
-            if constexpr (STASH) {
-                if (extra > 0 && 8 * g + 4 * h + 3 >= xs) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int q = 8 * g + 4 * h + u;
-                        if (q >= xs) stE[(q - xs) * 32 + j] = b[u];
-                    }
-                }
-            }
-            b = bn;
-        }
+            float aux3[3];
+            const float *auxrow;
+            aux_inputs(a, xrow, aux, row, valid, aux3, auxrow);
+            first_layer_generic<H, WLDS, STASH>(a, W0, xrow, aux3, auxrow, valid, j, h, act, stE, xs, extra);
         }
 #pragma unroll
         for (int ob = 0; ob < T; ++ob) {
             tn::pin16(act[ob]);
             act[ob] = tn::relu16(act[ob]);
-            if constexpr (STASH) { stM[ob * 64 + lane] = relu_bits(act[ob]); store_rows(stH, act[ob], ob, j, h); }
+            if constexpr (STASH) keep_relu<true>(act[ob], stM[ob * 64 + lane], stH, ob, j, h);
         }
         // ---- hidden layers H -> H ----
         for (int l = 1; l + 1 < L; ++l) {
@@ -514,10 +438,7 @@ __global__ __launch_bounds__(WPB * 64) void mlp_fwd_kernel(MlpArgs a0, const flo
             tn::hidden_layer<H>(Wl, Bl, WLDS ? a.stride[l] : H, act, j, h);
             if constexpr (STASH) {
 #pragma unroll
-                for (int ob = 0; ob < T; ++ob) {
-                    stM[(l * T + ob) * 64 + lane] = relu_bits(act[ob]);
-                    store_rows(stH + l * H * 32, act[ob], ob, j, h);
-                }
+                for (int ob = 0; ob < T; ++ob) keep_relu<true>(act[ob], stM[(l * T + ob) * 64 + lane], stH + l * H * 32, ob, j, h);
             }
         }
         // ---- output layer ----

@@ -19,6 +19,7 @@
 // Workspace: (2*NH*H + 4) rows of 128 B per 32 samples (2.06 KB/sample for the K-Planes colour head).
 #include "mlp_stage.h"
 #include "kplanes_scatter.h"
+#include "phase_timers.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -40,19 +41,9 @@ extern "C" int tn_mlp_wgrad_lean_check(const tn_mlp_desc *desc, const tn_mlp_des
 extern "C" int tn_mlp_wgrad_rows(const float *g_rows, int64_t g_stride, int ng, const float *a_rows, int64_t a_stride, int na, float *gW,
                                  int ldw, int col0, int kmax, float *gB, int64_t n, void *stream);
 
-#ifdef TN_PHASE_TIMERS
-__device__ unsigned long long tn_phase_cycles_b[16];
-#define TN_PTB_BEGIN unsigned long long ptb_ = __builtin_amdgcn_s_memtime();
-#define TN_PTB(k) { __builtin_amdgcn_sched_barrier(0); const unsigned long long n_ = __builtin_amdgcn_s_memtime(); if (tn::lane_id() == 0) atomicAdd(&tn_phase_cycles_b[k], n_ - ptb_); ptb_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-extern "C" int tn_debug_phase_cycles_b(unsigned long long *out, int reset) {
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(tn_phase_cycles_b), sizeof(unsigned long long) * 16);
-    if (reset) { unsigned long long z[16] = {}; hipMemcpyToSymbol(HIP_SYMBOL(tn_phase_cycles_b), z, sizeof(z)); }
-    return 0;
-}
-#else
-#define TN_PTB_BEGIN
-#define TN_PTB(k)
-#endif
+TN_PHASE_COUNTERS(tn_phase_cycles_b, tn_debug_phase_cycles_b)              // (scripts/phase_time_chain.py)
+#define TN_PTB_BEGIN TN_PHASE_BEGIN(ptb_)
+#define TN_PTB(k) TN_PHASE(tn_phase_cycles_b, ptb_, k)
 namespace {
 
 using tn::f32x16;
@@ -93,6 +84,7 @@ struct KpBwd {
     int64_t coord_stride;
 };
 
+// the first data-gradient step, out <= 4 outputs on the VALU: G = relu'(H_NH) * (W_f^T g_pre)
 template <int H>
 __device__ __forceinline__ void first_dgrad(const float *__restrict__ Wf, int sf, int out, const float (&gp)[4],
                                             const unsigned (&mask)[H / 32], int h, f32x16 (&G)[H / 32])
@@ -149,7 +141,6 @@ __global__ __launch_bounds__(WPB * 64) void mlp_chain_kernel(MlpArgs a, const fl
     const int lane = tn::lane_id(), j_ = lane & 31, h_ = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);     // wave-uniform: tile indices and workspace bases are scalars
     const int64_t n_tiles = (n + 31) >> 5;
-    const int G0 = a.K0_pad >> 3;
     const int out = a.out_dim;
 
     // STASHED: the per-tile inputs (ReLU masks, last pre-activation, output gradient) of the NEXT tile are requested at the
@@ -159,14 +150,14 @@ __global__ __launch_bounds__(WPB * 64) void mlp_chain_kernel(MlpArgs a, const fl
     float npre[4], ngy[4];
     unsigned bmask[T];
     float bpre[4], bgy[4];
-    const int Rb = stash_rows(H, 1, 0);                    // PAIR: workspace rows per tile of head b (NH = 1, no E rows)
-    const int extra_ = extra_rows(a.enc, a.in_dim, a.K0_pad);
+    const StashTile sb(H, 1, 0);                           // PAIR: head b's tiles (NH = 1, no E rows)
+    const StashTile sa(H, NH, a.enc, a.in_dim, a.K0_pad);
     auto fetch_tile = [&](int64_t t) {
         if constexpr (PAIR) {
-            const float *qb = pr.stash + t * (int64_t)(Rb * 32) + stash_rows_w(H, 1, 0) * 32;
-            const unsigned *mb = reinterpret_cast<const unsigned *>(qb + 4 * 32);
+            const float *tb = pr.stash + t * (int64_t)sb.floats(), *qb = tb + sb.pre();
+            const unsigned *mb = reinterpret_cast<const unsigned *>(tb + sb.masks());
 #pragma unroll
-            for (int ob = 0; ob < T; ++ob) bmask[ob] = mb[ob * 64 + lane];
+            for (int ob = 0; ob < T; ++ob) bmask[ob] = mb[sb.mask(0, ob) + lane];
             int64_t rb = t * 32 + j_;
             rb = rb < n ? rb : n - 1;
             const int outb = pr.b.out_dim;
@@ -177,12 +168,12 @@ __global__ __launch_bounds__(WPB * 64) void mlp_chain_kernel(MlpArgs a, const fl
                 bgy[o] = pr.gy[rb * outb + oc];
             }
         }
-        const float *q = stash + t * (int64_t)(stash_rows(H, NH, extra_) * 32) + stash_rows_w(H, NH, extra_) * 32;
-        const unsigned *mm = reinterpret_cast<const unsigned *>(q + 4 * 32);
+        const float *ta = stash + t * (int64_t)sa.floats(), *q = ta + sa.pre();
+        const unsigned *mm = reinterpret_cast<const unsigned *>(ta + sa.masks());
 #pragma unroll
         for (int l = 0; l < NH; ++l)
 #pragma unroll
-            for (int ob = 0; ob < T; ++ob) nmask[l][ob] = mm[(l * T + ob) * 64 + lane];
+            for (int ob = 0; ob < T; ++ob) nmask[l][ob] = mm[sa.mask(l, ob) + lane];
         int64_t r = t * 32 + j_;
         r = r < n ? r : n - 1;
 #pragma unroll
@@ -203,14 +194,8 @@ __global__ __launch_bounds__(WPB * 64) void mlp_chain_kernel(MlpArgs a, const fl
         TN_PTB_BEGIN
         const int64_t row = tile * 32 + j;
         const bool valid = row < n;
-        const int extra = extra_rows(a.enc, a.in_dim, a.K0_pad);
-        float *st = stash + tile * (int64_t)(stash_rows(H, NH, extra) * 32);
-        float *stH = st;                                // H_1 .. H_NH
-        float *stG = st + NH * H * 32;                  // G_0 .. G_{NH-1}
-        float *stP = st + 2 * NH * H * 32;              // g_pre (4 rows)
-        float *stE = stP + 4 * 32;                      // encoded extras
-        float *stQ = st + stash_rows_w(H, NH, extra) * 32;             // pre-activation of the last layer (4 rows)
-        unsigned *stM = reinterpret_cast<unsigned *>(stQ + 4 * 32);    // ReLU masks
+        float *st = stash + tile * (int64_t)sa.floats();
+        float *stH = st, *stG = st + sa.g(0), *stP = st + sa.g_pre(), *stE = st + sa.e();
         const float *Wf = lds + a.w_off[L - 1];
         const float *Bf = lds + a.b_off[L - 1];
         const int sf = a.stride[L - 1];
@@ -236,73 +221,41 @@ __global__ __launch_bounds__(WPB * 64) void mlp_chain_kernel(MlpArgs a, const fl
                 fetch_tile(tn_ < n_tiles ? tn_ : n_tiles - 1);       // before this tile's stores
             }
             if constexpr (PAIR) {                                    // head b: g_pre rows, G_0 = relu'(H_1) * (W_1^T g_pre), G_0 rows
-                float *stb = pr.stash + tile * (int64_t)(Rb * 32);
+                float *stb = pr.stash + tile * (int64_t)sb.floats();
 #pragma unroll
                 for (int o = 0; o < 4; ++o)
-                    if (h == 0) stb[(2 * H + o) * 32 + j] = gpb[o];
+                    if (h == 0) stb[sb.g_pre() + o * 32 + j] = gpb[o];
                 f32x16 Gb[T];
                 first_dgrad<H>(ldsb + pr.b.w_off[1], pr.b.stride[1], pr.b.out_dim, gpb, pmask, h, Gb);
 #pragma unroll
-                for (int ob = 0; ob < T; ++ob) store_rows(stb + H * 32, Gb[ob], ob, j, h);
+                for (int ob = 0; ob < T; ++ob) store_rows(stb + sb.g(0), Gb[ob], ob, j, h);
                 // (G_0b is rebuilt from g_pre and the mask where grad_x needs it: 6 live registers instead of 32)
             }
 #pragma unroll
             for (int o = 0; o < 4; ++o)
                 if (h == 0) stP[o * 32 + j] = gp[o];
-            (void)stQ; (void)stM;
         } else {
         const float *xrow = x + (valid ? row : 0) * a.in_dim;
-        float aux3[3] = {0.f, 0.f, 0.f};
-        const float *auxrow = nullptr;
-        if (valid) {
-            if (a.enc == TN_ENC_POSENC) { aux3[0] = xrow[0]; aux3[1] = xrow[1]; aux3[2] = xrow[2]; }
-            else if (a.enc == TN_ENC_DIR_CAT) { aux3[0] = aux[3 * row]; aux3[1] = aux[3 * row + 1]; aux3[2] = aux[3 * row + 2]; }
-            else if (a.enc == TN_ENC_AUX_CAT) auxrow = aux + (int64_t)(a.aux_index ? a.aux_index[row] : row) * a.aux_stride;
-        }
-        const int xs = x_slots(a.enc, a.in_dim);
+        float aux3[3];
+        const float *auxrow;
+        aux_inputs(a, xrow, aux, row, valid, aux3, auxrow);
 
         // ---------------- forward ----------------
         f32x16 act[T];
-        {
-            const float *W0 = lds + a.w_off[0];
 #pragma unroll
-            for (int ob = 0; ob < T; ++ob) act[ob] = tn::bias_tile(lds + a.b_off[0], ob, h);
-            f32x4 b = fetch_input(a, xrow, aux3, valid, 0, h, auxrow);
-            for (int g = 0; g < G0; ++g) {
-                f32x4 bn = {0.f, 0.f, 0.f, 0.f};
-                if (g + 1 < G0) bn = fetch_input(a, xrow, aux3, valid, g + 1, h, auxrow);
-                f32x4 w[T];
+        for (int ob = 0; ob < T; ++ob) act[ob] = tn::bias_tile(lds + a.b_off[0], ob, h);
+        first_layer_generic<H, true, true>(a, lds + a.w_off[0], xrow, aux3, auxrow, valid, j, h, act, stE, x_slots(a.enc, a.in_dim), sa.extra);
 #pragma unroll
-                for (int ob = 0; ob < T; ++ob) w[ob] = load_a4<true>(W0, 32 * ob + j, 8 * g + 4 * h, a.K0, a.stride[0]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int ob = 0; ob < T; ++ob) act[ob] = tn::mfma32(w[ob][u], b[u], act[ob]);
-                if (extra > 0 && 8 * g + 4 * h + 3 >= xs) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int q = 8 * g + 4 * h + u;
-                        if (q >= xs) stE[(q - xs) * 32 + j] = b[u];
-                    }
-                }
-                b = bn;
-            }
-#pragma unroll
-            for (int ob = 0; ob < T; ++ob) {
-                tn::pin16(act[ob]);
-                act[ob] = tn::relu16(act[ob]);
-                mask[0][ob] = relu_bits(act[ob]);
-                store_rows(stH, act[ob], ob, j, h);
-            }
+        for (int ob = 0; ob < T; ++ob) {
+            tn::pin16(act[ob]);
+            act[ob] = tn::relu16(act[ob]);
+            keep_relu<true>(act[ob], mask[0][ob], stH, ob, j, h);
         }
         static_for<NH - 1>([&](auto lc) {
             constexpr int l = decltype(lc)::value + 1;          // layer l: H_l -> H_{l+1}
             tn::hidden_layer<H>(lds + a.w_off[l], lds + a.b_off[l], a.stride[l], act, j, h);
 #pragma unroll
-            for (int ob = 0; ob < T; ++ob) {
-                mask[l][ob] = relu_bits(act[ob]);
-                store_rows(stH + l * H * 32, act[ob], ob, j, h);
-            }
+            for (int ob = 0; ob < T; ++ob) keep_relu<true>(act[ob], mask[l][ob], stH + sa.h(l), ob, j, h);
         });
 
         // ---------------- output gradient (out <= 4) and first data-gradient step on the VALU ----------------
@@ -318,36 +271,18 @@ __global__ __launch_bounds__(WPB * 64) void mlp_chain_kernel(MlpArgs a, const fl
         }
         TN_PTB(0)
         f32x16 G[T];
-#pragma unroll
-        for (int kb = 0; kb < T; ++kb) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 acc4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int o = 0; o < 4; ++o) {
-                    if (o < out) {
-                        const f32x4 w = *reinterpret_cast<const f32x4 *>(Wf + o * sf + 32 * kb + 8 * q + 4 * h);
-                        acc4 += w * gp[o];
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) G[kb][4 * q + u] = mask_keep(acc4[u], mask[NH - 1][kb], 4 * q + u);
-            }
-        }
+        first_dgrad<H>(Wf, sf, out, gp, mask[NH - 1], h, G);
 
         // ---------------- hidden layers, last to first ----------------
         static_for<NH - 1>([&](auto lc) {
             constexpr int l = NH - 1 - decltype(lc)::value;     // l = NH-1 .. 1 : G holds G_l
 #pragma unroll
-            for (int ob = 0; ob < T; ++ob) store_rows(stG + l * H * 32, G[ob], ob, j, h);
+            for (int ob = 0; ob < T; ++ob) store_rows(st + sa.g(l), G[ob], ob, j, h);
             const float *Wl = lds + a.w_off[l];
             constexpr int sl = H + 4;                       // stride of every hidden layer (mlp_stage.h plan()): a constant lets the
                                                             // row offsets below become ds_read immediates instead of VALU adds
             f32x16 Gn[T];
-#pragma unroll
-            for (int kt = 0; kt < T; ++kt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) Gn[kt][r] = 0.0f;
+            tn::zero_tiles(Gn);
             // software pipeline over the 4T groups (tn_, q): operands of group g+1 are requested before group g's MFMAs
             {
                 constexpr int NG = 4 * T;
@@ -414,8 +349,7 @@ __global__ __launch_bounds__(WPB * 64) void mlp_chain_kernel(MlpArgs a, const fl
 #pragma clang loop unroll(disable)
             for (int kt = 0; kt < n_kt; ++kt) {
                 f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+                tn::zero_tile(acc);
                 if constexpr (ACCUM) {
                     if (gxr != nullptr) tn::mlp::load_rows(gxr + kt * 32 * 32, acc, 0, j, h);     // the MFMAs below accumulate on top
                 }
@@ -538,12 +472,38 @@ struct WgradArgs {
     int K[TN_MLP_MAX_LAYERS], N[TN_MLP_MAX_LAYERS];
 };
 
-__device__ __forceinline__ int wg_col0(const WgradArgs &a, int q) {
-    if (a.enc == TN_ENC_DIR_CAT || a.enc == TN_ENC_AUX_CAT) {
-        const int pe = a.K0 - a.in_dim;
-        return q < a.in_dim ? pe + q : q - a.in_dim;
+constexpr int RS = 36;      // LDS row stride in floats: 16-B aligned rows, conflict-free ds_read_b128 across 16 lanes
+
+// first layer, slot q: its operand is a column of the sample-major x rows (ldsX) or aux-table rows (ldsA) of this half's 16 samples;
+// neither (cp stays null): an encoded slot or padding
+template <bool AUX>
+__device__ __forceinline__ void first_layer_column(const WgradArgs &a, int q, int xs, int aw, const float *ldsX, const float *ldsA, int h,
+                                                   const float *&cp, int &cstride)
+{
+    if (q < xs) { cp = ldsX + 16 * h * a.in_dim + q; cstride = a.in_dim; }
+    else if (AUX && q < a.K0_pad) { cp = ldsA + 16 * h * aw + (q - xs); cstride = aw; }
+}
+
+// One accumulator tile (layer l, row block tn_, k block tk) into the gradients: full-line atomics (lanes = consecutive columns of one
+// weight row); the k block 0 of a row block also carries the bias gradient, the row sums of G.  The column pointer is formed once,
+// outside the register loop.
+__device__ __forceinline__ void flush_tile(const WgradArgs &a, int l, int tn_, int tk, f32x16 &acc, float dbsum, int i, int h)
+{
+    tn::pin16(acc);
+    const int Nl = a.N[l], Kl = a.K[l];
+    const int k = 32 * tk + i;
+    const bool kok = k < Kl;
+    float *col = a.gW[l] + (kok ? (l == 0 ? layer0_col(a.enc, a.K0, a.in_dim, k) : k) : 0);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int nn = 32 * tn_ + tn::frow(r, h);
+        if (kok && nn < Nl) atomicAdd(col + (int64_t)nn * Kl, acc[r]);
     }
-    return q;
+    if (tk == 0) {
+        dbsum += __shfl_xor(dbsum, 32, 64);
+        const int nn = 32 * tn_ + i;
+        if (h == 0 && nn < Nl) atomicAdd(&a.gB[l][nn], dbsum);
+    }
 }
 
 // Tile id -> (layer, tn, tk).  Order: layer 0 tiles (tn-major), hidden layers, last layer.
@@ -563,8 +523,6 @@ __device__ __forceinline__ void decode_tile(const WgradArgs &a, int id, int &l, 
 // LDS, so every byte is read from HBM exactly once (PMC: reading operands straight from global re-fetched each
 // row ~2x), then each wave runs the MFMA tiles it owns (tile id = wave + NW*m) from LDS.  The next tile is
 // prefetched into registers while the current one is being multiplied (issue early / write late).
-constexpr int RS = 36;      // LDS row stride in floats: 16-B aligned rows, conflict-free ds_read_b128 across 16 lanes
-
 template <int H, int NH, int MAXS, int NW, int NCH, bool AUX>
 __global__ __launch_bounds__(NW * 64) void mlp_wgrad_kernel(WgradArgs a, const float *__restrict__ x, const float *__restrict__ aux,
                                                             int64_t n, const float *__restrict__ stash)
@@ -575,9 +533,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad_kernel(WgradArgs a, const f
     const int64_t n_tiles = (n + 31) >> 5;
     const int xs = x_slots(a.enc, a.in_dim);
     const int xs_st = 32 * a.tk_skip >= xs ? 0 : xs;      // x columns that are this kernel's: staged sample-major (none when skipped)
-    const int extra = extra_rows(a.enc, a.in_dim, a.K0_pad);
-    const int R = stash_rows_w(H, NH, extra);             // rows staged per tile
-    const int Rt = stash_rows(H, NH, extra);              // rows per tile in the workspace
+    const StashTile st(H, NH, a.enc, a.in_dim, a.K0_pad);
+    const int extra = st.extra;
+    const int R = st.rows_w();                            // rows staged per tile
     const int row_chunks = R * 8;                         // float4 chunks of the workspace tile
     const int x_chunks = xs_st > 0 ? (32 * a.in_dim) / 4 : 0;   // float4 chunks of the x rows of the tile (contiguous)
     const int aw = AUX ? a.K0_pad - a.in_dim : 0;         // aux-table columns (multiple of 8, <= 64)
@@ -587,10 +545,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad_kernel(WgradArgs a, const f
     f32x16 acc[MAXS];
     float dbacc[MAXS];
     int tl[MAXS], ttn[MAXS], ttk[MAXS];
+    tn::zero_tiles(acc);
 #pragma unroll
     for (int m = 0; m < MAXS; ++m) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[m][r] = 0.0f;
         dbacc[m] = 0.0f;
         tl[m] = -1; ttn[m] = 0; ttk[m] = 0;
         const int id = wave + NW * m;
@@ -603,8 +560,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad_kernel(WgradArgs a, const f
     // Every load below is unconditional (addresses clamped into valid memory, results of idle slots never committed):
     // a load whose result is merged with a constant at a control-flow join makes the compiler wait for it right there
     // (s_waitcnt vmcnt(0) after every load), which serialises the prefetch with the MFMA phase it is meant to overlap.
+    // (The chunk loop stands in both weight-gradient kernels: as one helper it cost this kernel 7 - 11 us per call, LABNOTES 9.11.)
     auto prefetch = [&](int64_t tile) {
-        const f32x4 *src = reinterpret_cast<const f32x4 *>(stash + tile * (int64_t)Rt * 32);
+        const f32x4 *src = reinterpret_cast<const f32x4 *>(stash + tile * (int64_t)st.floats());
         const int64_t x0 = tile * 32 * (int64_t)a.in_dim;          // first float of the tile's x rows
         const int64_t xlast = n * (int64_t)a.in_dim - 4;           // in_dim % 4 == 0: chunks never straddle the end
 #pragma unroll
@@ -645,14 +603,14 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad_kernel(WgradArgs a, const f
         if (tile + gridDim.x < n_tiles) prefetch(tile + gridDim.x);      // in flight during the MFMAs below
         int i = i_, h = h_;
         asm volatile("" : "+v"(i), "+v"(h));     // per-lane LDS addresses are rebuilt per tile, not kept live (spills)
-        const float *rowsE = ldsR + (2 * NH * H + 4) * RS;
+        const float *rowsE = ldsR + (st.e() / 32) * RS;
 #pragma unroll
         for (int m = 0; m < MAXS; ++m) {
             const int l = tl[m];
             if (l < 0) continue;
             // G operand: row segment [16 samples of this half]; A-side operand: a row segment (hidden layers, E rows) or
             // a column of the sample-major x / aux rows.  Four samples (one e) at a time keeps the live set small.
-            const int grow = l < NH ? (NH + l) * H + 32 * ttn[m] + i : 2 * NH * H + (i < 4 ? i : 0);
+            const int grow = l < NH ? st.g(l) / 32 + 32 * ttn[m] + i : st.g_pre() / 32 + (i < 4 ? i : 0);
             const f32x4 *gp = reinterpret_cast<const f32x4 *>(ldsR + grow * RS + 16 * h);
             const bool gok = l < NH || i < 4;
             const f32x4 *rp = nullptr;           // row-type source
@@ -660,11 +618,10 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad_kernel(WgradArgs a, const f
             int cstride = 0;
             if (l == 0) {
                 const int q = 32 * ttk[m] + i;
-                if (q < xs) { cp = ldsX + 16 * h * a.in_dim + q; cstride = a.in_dim; }
-                else if (AUX && q < a.K0_pad) { cp = ldsA + 16 * h * aw + (q - xs); cstride = aw; }
-                else if (!AUX && extra > 0 && q < a.K0_pad) rp = reinterpret_cast<const f32x4 *>(rowsE + (q - xs) * RS + 16 * h);
+                first_layer_column<AUX>(a, q, xs, aw, ldsX, ldsA, h, cp, cstride);
+                if (!AUX && q >= xs && extra > 0 && q < a.K0_pad) rp = reinterpret_cast<const f32x4 *>(rowsE + (q - xs) * RS + 16 * h);
             } else {
-                rp = reinterpret_cast<const f32x4 *>(ldsR + ((l - 1) * H + 32 * ttk[m] + i) * RS + 16 * h);
+                rp = reinterpret_cast<const f32x4 *>(ldsR + (st.h(l - 1) / 32 + 32 * ttk[m] + i) * RS + 16 * h);
             }
             float gsum = 0.f;
 #pragma unroll
@@ -685,29 +642,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad_kernel(WgradArgs a, const f
             if (ttk[m] == 0) dbacc[m] += gsum;
         }
     }
-    // ---- flush: full-line atomics (lanes = consecutive columns of one weight row) ----
-    const int i = i_, h = h_;
 #pragma unroll
-    for (int m = 0; m < MAXS; ++m) {
-        const int l = tl[m];
-        if (l < 0) continue;
-        tn::pin16(acc[m]);
-        const int Nl = a.N[l], Kl = a.K[l];
-        const int k = 32 * ttk[m] + i;
-        const bool kok = k < Kl;
-        const int kc = kok ? (l == 0 ? wg_col0(a, k) : k) : 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int nn = 32 * ttn[m] + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (kok && nn < Nl) atomicAdd(&a.gW[l][(int64_t)nn * Kl + kc], acc[m][r]);
-        }
-        if (ttk[m] == 0) {
-            float sum = dbacc[m];
-            sum += __shfl_xor(sum, 32, 64);
-            const int nn = 32 * ttn[m] + i;
-            if (h == 0 && nn < Nl) atomicAdd(&a.gB[l][nn], sum);
-        }
-    }
+    for (int m = 0; m < MAXS; ++m)
+        if (tl[m] >= 0) flush_tile(a, tl[m], ttn[m], ttk[m], acc[m], dbacc[m], i_, h_);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -739,7 +676,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad4_kernel(WgradArgs a, const 
     const int xs = a.in_dim;
     constexpr int RG = H + NH * H + 4;                    // staged workspace rows: H_NH, G_0 .. G_{NH-1}, g_pre
     constexpr int R0 = (NH - 1) * H;                      // first staged row of a tile
-    const int Rt = stash_rows(H, NH, 0);
+    const int Rt = StashTile(H, NH, 0).rows();
     constexpr int g_chunks = RG * 8;
     // tk_skip > 0 (round 4): the first layer's x tiles -- k tiles below in_dim / 32 -- are computed by the row-operand kernel
     // from the feature stack's workspace (mlp_wgrad_rows.hip); here only its table columns are left and no x rows are staged
@@ -755,10 +692,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad4_kernel(WgradArgs a, const 
     else if (wave == T0 + (NH - 1) * T) { kind = 2; l = NH; }
     f32x16 acc[2];
     float dbacc[2] = {0.f, 0.f};
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[m][r] = 0.0f;
+    tn::zero_tiles(acc);
     f32x4 pre[NCH];
     f32x4 preA = {0.f, 0.f, 0.f, 0.f};
     f32x4 hn[4];
@@ -851,11 +785,7 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad4_kernel(WgradArgs a, const 
             }
             const float *cp = nullptr;      // first layer: a column of the sample-major x / aux rows
             int cstride = 0;
-            if (kind == 0) {
-                const int q = 32 * tk + i;
-                if (q < xs) { cp = ldsX + 16 * h * a.in_dim + q; cstride = a.in_dim; }
-                else if (AUX && q < a.K0_pad) { cp = ldsA + 16 * h * aw + (q - xs); cstride = aw; }
-            }
+            if (kind == 0) first_layer_column<AUX>(a, 32 * tk + i, xs, aw, ldsX, ldsA, h, cp, cstride);
             const f32x4 *r0 = reinterpret_cast<const f32x4 *>(buf + i * RS + 16 * h);            // last layer: H_NH rows tk = 0
             const f32x4 *r1 = reinterpret_cast<const f32x4 *>(buf + (32 + i) * RS + 16 * h);     //                       tk = 1
             float gs0 = 0.f, gs1 = 0.f;
@@ -885,29 +815,9 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad4_kernel(WgradArgs a, const 
         __syncthreads();
         cur ^= 1;
     }
-    // ---- flush ----
     if (kind < 0) return;
-    const int i = i_, h = h_;
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        tn::pin16(acc[m]);
-        const int tn_ = kind == 2 ? 0 : m, tkm = kind == 2 ? m : tk;
-        const int Nl = a.N[l], Kl = a.K[l];
-        const int k = 32 * tkm + i;
-        const bool kok = k < Kl;
-        const int kc = kok ? (l == 0 ? wg_col0(a, k) : k) : 0;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int nn = 32 * tn_ + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (kok && nn < Nl) atomicAdd(&a.gW[l][(int64_t)nn * Kl + kc], acc[m][r]);
-        }
-        if (tkm == 0) {                                   // bias gradient: row sums of G (once per row block)
-            float sum = dbacc[m];
-            sum += __shfl_xor(sum, 32, 64);
-            const int nn = 32 * tn_ + i;
-            if (h == 0 && nn < Nl) atomicAdd(&a.gB[l][nn], sum);
-        }
-    }
+    for (int m = 0; m < 2; ++m) flush_tile(a, l, kind == 2 ? 0 : m, kind == 2 ? m : tk, acc[m], dbacc[m], i_, h_);      // (last layer: one row block, two k blocks)
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -917,8 +827,8 @@ __global__ __launch_bounds__(NW * 64) void mlp_wgrad4_kernel(WgradArgs a, const 
 struct WgradPlan { int R, Rt, xs, aw, chunks; size_t lds; };
 WgradPlan wgrad_plan(int enc, int in_dim, int K0_pad, int H, int NH, bool x_elsewhere = false) {
     WgradPlan p;
-    const int extra = extra_rows(enc, in_dim, K0_pad);
-    p.R = stash_rows_w(H, NH, extra); p.Rt = stash_rows(H, NH, extra);
+    const StashTile st(H, NH, enc, in_dim, K0_pad);
+    p.R = st.rows_w(); p.Rt = st.rows();
     p.xs = x_elsewhere ? 0 : x_slots(enc, in_dim);         // x columns taken from row views: nothing of x is staged here
     p.aw = enc == TN_ENC_AUX_CAT ? K0_pad - in_dim : 0;
     p.chunks = p.R * 8 + (p.xs > 0 ? 8 * in_dim : 0);           // float4 chunks of workspace rows + x rows per tile
@@ -933,15 +843,7 @@ MlpArgs compact_first_layer(const MlpArgs &a)
     MlpArgs c = a;
     const int H = a.N[0];
     c.K0_pad = (a.in_dim + 7) & ~7;
-    int off = 0;
-    for (int l = 0; l < a.n_layers; ++l) {
-        const int Kp = l == 0 ? c.K0_pad : H;
-        const int rows = (l == a.n_layers - 1) ? (a.out_dim <= 4 ? a.out_dim : ((a.out_dim + 31) & ~31)) : H;
-        c.stride[l] = Kp + 4;
-        c.w_off[l] = off; off += rows * c.stride[l];
-        c.b_off[l] = off; off += (rows + 3) & ~3;
-    }
-    c.lds_floats = off;
+    lay_out_lds(c, H);
     return c;
 }
 
@@ -967,8 +869,9 @@ int launch_chain_g0b(const MlpArgs &b, const MlpArgs &a, const float *x, const f
 }
 
 // Workspace geometry of a width-64 head (two-pass form): floats per 32-sample tile, and where its G_0 rows start
-int64_t tile_floats(const MlpArgs &m) { return (int64_t)stash_rows(64, m.n_layers - 1, extra_rows(m.enc, m.in_dim, m.K0_pad)) * 32; }
-int64_t g0_floats(const MlpArgs &m) { return (int64_t)(m.n_layers - 1) * 64 * 32; }
+StashTile stash_tile(const MlpArgs &m) { return StashTile(64, m.n_layers - 1, m.enc, m.in_dim, m.K0_pad); }
+int64_t tile_floats(const MlpArgs &m) { return stash_tile(m).floats(); }
+int64_t g0_floats(const MlpArgs &m) { return stash_tile(m).g(0); }
 
 // The first layer's x-column weight gradient comes from x as rows of the producer's workspace (mlp_wgrad_rows.hip) ...
 bool x_cols_from_rows(const MlpArgs &a, bool stashed) {
@@ -1121,8 +1024,7 @@ extern "C" int64_t tn_mlp_bwd_workspace_bytes(const tn_mlp_desc *desc, int64_t n
         return tn_mlp_bwd_layers_workspace_bytes(desc, n);
     }
     const int H = desc->dims[1], NH = desc->n_layers - 1;
-    const int extra = extra_rows(desc->encoding, desc->in_dim, (desc->dims[0] + 7) & ~7);
-    return ((n + 31) / 32) * (int64_t)stash_rows(H, NH, extra) * 32 * (int64_t)sizeof(float);
+    return ((n + 31) / 32) * (int64_t)StashTile(H, NH, desc->encoding, desc->in_dim, (desc->dims[0] + 7) & ~7).floats() * (int64_t)sizeof(float);
 }
 
 extern "C" int tn_mlp_bwd(const tn_mlp_desc *desc, const float *x, const float *aux, const float *grad_y, int64_t n,

@@ -39,6 +39,21 @@ __device__ __forceinline__ f32x16 bias_tile(const float *bias, int ob, int h) {
     return y;
 }
 
+__device__ __forceinline__ void zero_tile(f32x16 &t) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) t[r] = 0.0f;
+}
+template <int N>
+__device__ __forceinline__ void zero_tiles(f32x16 (&t)[N]) {
+#pragma unroll
+    for (int m = 0; m < N; ++m) zero_tile(t[m]);
+}
+
+// max(m, largest |v|) of four values
+__device__ __forceinline__ float max_abs4(float m, const f32x4 &v) {
+    return fmaxf(fmaxf(m, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
+}
+
 // Materialise an MFMA result in VGPRs HERE, in straight-line code.  hipcc (ROCm 7.2) counts the MFMA ->
 // v_accvgpr_read wait states along the longest predecessor path only: when a branch sits between the last
 // MFMA and the first read of its accumulator, the short path reads a[15] (written in the final pass) too

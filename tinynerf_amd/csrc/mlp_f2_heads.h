@@ -49,6 +49,11 @@ __device__ __forceinline__ void f2_split8(const float (&v)[8], float s, u32x4h &
         lo[p] = __builtin_bit_cast(unsigned, ll);
     }
 }
+// ... from two f32x4: slots 8g + 4h .. + 3 of the block's two groups
+__device__ __forceinline__ void f2_split8(f32x4 v0, f32x4 v1, float s, u32x4h &hi, u32x4h &lo) {
+    const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    f2_split8(v, s, hi, lo);
+}
 __device__ __forceinline__ float f2_xmax(float m) { return fmaxf(m, __shfl_xor(m, 32, 64)); }      // both halves of a sample's column
 
 // position of first-layer / hidden slot q inside a staged row: [k block][half][8]
@@ -148,7 +153,7 @@ __device__ __forceinline__ void hidden_layer_f2(const float *__restrict__ ldsw, 
     f2_scales(f2_xmax(m), s, inv);
     f32x16 y[2];
 #pragma unroll
-    for (int ob = 0; ob < 2; ++ob)
+    for (int ob = 0; ob < 2; ++ob)          // (spelt out: through tn::zero_tiles three of the f16x2 forward kernels convert the activations with another instruction mix)
 #pragma unroll
         for (int r = 0; r < 16; ++r) y[ob][r] = 0.0f;
 #pragma unroll

@@ -39,13 +39,14 @@ struct MlpArgs {
 };
 
 // column of the torch weight matrix that feeds first-layer slot q (slot order: see fetch_input)
-__device__ __forceinline__ int layer0_col(const MlpArgs &a, int q) {
-    if (a.enc == TN_ENC_DIR_CAT || a.enc == TN_ENC_AUX_CAT) {
-        const int pe = a.K0 - a.in_dim;                    // 6F + 3 for the colour head
-        return q < a.in_dim ? pe + q : q - a.in_dim;       // torch order: [PE(d), d, feat]
+__device__ __forceinline__ int layer0_col(int enc, int K0, int in_dim, int q) {
+    if (enc == TN_ENC_DIR_CAT || enc == TN_ENC_AUX_CAT) {
+        const int pe = K0 - in_dim;                        // 6F + 3 for the colour head
+        return q < in_dim ? pe + q : q - in_dim;           // torch order: [PE(d), d, feat]
     }
     return q;
 }
+__device__ __forceinline__ int layer0_col(const MlpArgs &a, int q) { return layer0_col(a.enc, a.K0, a.in_dim, q); }
 
 // copy every layer into LDS: [rows][K_pad + 4] + bias, zero padded
 __device__ inline void stage_weights(const MlpArgs &a, float *lds) {
@@ -120,13 +121,27 @@ constexpr int LDS_LIMIT_BYTES = 160 * 1024;
 // Rows of [32 samples] floats (128 B) per 32-sample tile:
 //   H_1..H_NH | G_0..G_{NH-1} | g_pre (4) | E (encoded first-layer slots of TN_ENC_DIR_CAT / POSENC that are not plain
 //   x columns) | pre (4, last layer's pre-activation) | ReLU bit masks (2 rows per (layer, 32-feature block))
-// The weight-gradient kernel stages the first stash_rows_w() rows; pre and masks are for the chain kernel only.
+// The weight-gradient kernel stages the first StashTile::rows_w() rows; pre and masks are for the chain kernel only.
 __host__ __device__ inline int x_slots(int enc, int in_dim) { return enc == TN_ENC_POSENC ? 0 : in_dim; }
 __host__ __device__ inline int extra_rows(int enc, int in_dim, int K0_pad) {
     return (enc == TN_ENC_NONE || enc == TN_ENC_AUX_CAT) ? 0 : K0_pad - x_slots(enc, in_dim);
 }
-__host__ __device__ inline int stash_rows_w(int H, int nh, int extra) { return 2 * nh * H + 4 + extra; }
-__host__ __device__ inline int stash_rows(int H, int nh, int extra) { return stash_rows_w(H, nh, extra) + 4 + 2 * nh * (H / 32); }
+// the row groups of a tile: rows counted from the tile's first row, offsets in floats from its first float
+struct StashTile {
+    int H, NH, extra;
+    __host__ __device__ StashTile(int H_, int NH_, int extra_) : H(H_), NH(NH_), extra(extra_) {}
+    __host__ __device__ StashTile(int H_, int NH_, int enc, int in_dim, int K0_pad) : H(H_), NH(NH_), extra(extra_rows(enc, in_dim, K0_pad)) {}
+    __host__ __device__ int rows_w() const { return 2 * NH * H + 4 + extra; }                     // what the weight-gradient kernel stages
+    __host__ __device__ int rows() const { return rows_w() + 4 + 2 * NH * (H / 32); }
+    __host__ __device__ int floats() const { return rows() * 32; }
+    __host__ __device__ int h(int l) const { return l * H * 32; }                                 // H_{l+1}
+    __host__ __device__ int g(int l) const { return (NH + l) * H * 32; }                          // G_l
+    __host__ __device__ int g_pre() const { return 2 * NH * H * 32; }
+    __host__ __device__ int e() const { return (2 * NH * H + 4) * 32; }
+    __host__ __device__ int pre() const { return rows_w() * 32; }
+    __host__ __device__ int masks() const { return (rows_w() + 4) * 32; }
+    __host__ __device__ int mask(int l, int ob) const { return (l * (H / 32) + ob) * 64; }        // in words behind masks(), + lane
+};
 
 // D-layout tile -> workspace rows [feature][32 samples]; two fully used 128-B lines per store instruction
 // `rows` is wave-uniform at every call site (a wave owns its tile): the stores take the SGPR-base form -- uniform 64-bit base,
@@ -182,6 +197,81 @@ __device__ __forceinline__ float mask_keep(float x, unsigned mask, int r) {
     return __uint_as_float(__float_as_uint(x) & (unsigned)keep);
 }
 
+// ReLU bits of a layer's output tile into `bits`, and (ROWS) the tile into the workspace rows
+template <bool ROWS>
+__device__ __forceinline__ void keep_relu(const f32x16 &t, unsigned &bits, float *rows, int ob, int j, int h) {
+    bits = relu_bits(t);
+    if constexpr (ROWS) store_rows(rows, t, ob, j, h);
+}
+
+// inference: nothing downstream sees rows whose gate is 0 -- a tile whose gates are all 0 gets zeros and is skipped (-> true)
+__device__ __forceinline__ bool gate_skips_tile(const MlpArgs &a, int64_t row, bool valid, int h, float *__restrict__ y, float *__restrict__ pre_act) {
+    if (a.row_gate == nullptr) return false;
+    const float gate = valid ? a.row_gate[row] : 0.0f;
+    if (__any(gate != 0.0f)) return false;
+    if (valid && h == 0) {
+        for (int o = 0; o < a.out_dim; ++o) {
+            y[row * a.out_dim + o] = 0.0f;
+            if (pre_act) pre_act[row * a.out_dim + o] = 0.0f;
+        }
+    }
+    return true;
+}
+
+// what fetch_input needs beside the x row: the point / direction of the fused encodings, or the sample's table row
+__device__ __forceinline__ void aux_inputs(const MlpArgs &a, const float *__restrict__ xrow, const float *__restrict__ aux, int64_t row,
+                                           bool valid, float (&aux3)[3], const float *&auxrow) {
+    aux3[0] = aux3[1] = aux3[2] = 0.f;
+    auxrow = nullptr;
+    if (!valid) return;
+    if (a.enc == TN_ENC_POSENC) { aux3[0] = xrow[0]; aux3[1] = xrow[1]; aux3[2] = xrow[2]; }
+    else if (a.enc == TN_ENC_DIR_CAT) { aux3[0] = aux[3 * row]; aux3[1] = aux[3 * row + 1]; aux3[2] = aux[3 * row + 2]; }
+    else if (a.enc == TN_ENC_AUX_CAT) auxrow = aux + (int64_t)(a.aux_index ? a.aux_index[row] : row) * a.aux_stride;
+}
+
+// The first layer on any encoding: act (holding the bias) += W_0 enc(x), inputs streamed 4 slots at a time and fetched one group
+// ahead.  STASH: the encoded slots that are no plain x column (slot >= xs, `extra` of them) also go to the E rows `stE`.
+template <int H, bool WLDS, bool STASH>
+__device__ __forceinline__ void first_layer_generic(const MlpArgs &a, const float *__restrict__ W0, const float *__restrict__ xrow,
+                                                    const float (&aux3)[3], const float *__restrict__ auxrow, bool valid, int j, int h,
+                                                    f32x16 (&act)[H / 32], float *__restrict__ stE, int xs, int extra)
+{
+    constexpr int T = H / 32;
+    const int G0 = a.K0_pad >> 3;
+    f32x4 b = fetch_input(a, xrow, aux3, valid, 0, h, auxrow);
+    for (int g = 0; g < G0; ++g) {
+        f32x4 bn = {0.f, 0.f, 0.f, 0.f};
+        if (g + 1 < G0) bn = fetch_input(a, xrow, aux3, valid, g + 1, h, auxrow);
+        f32x4 w[T];
+#pragma unroll
+        for (int ob = 0; ob < T; ++ob) {
+            if constexpr (WLDS) w[ob] = load_a4<true>(W0, 32 * ob + j, 8 * g + 4 * h, a.K0, a.stride[0]);
+            else if (a.enc != TN_ENC_DIR_CAT && a.enc != TN_ENC_AUX_CAT) w[ob] = load_a4<false>(W0, 32 * ob + j, 8 * g + 4 * h, a.K0, a.K0);
+            else {   // global first layer of a dir_cat head: slot -> torch column, one dword at a time
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int q = 8 * g + 4 * h + u;
+                    w[ob][u] = q < a.K0 ? W0[(int64_t)(32 * ob + j) * a.K0 + layer0_col(a, q)] : 0.0f;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int ob = 0; ob < T; ++ob) act[ob] = tn::mfma32(w[ob][u], b[u], act[ob]);
+        if constexpr (STASH) {
+            if (extra > 0 && 8 * g + 4 * h + 3 >= xs) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int q = 8 * g + 4 * h + u;
+                    if (q >= xs) stE[(q - xs) * 32 + j] = b[u];
+                }
+            }
+        }
+        b = bn;
+    }
+}
+
 // Configurations of the two-pass backward (chain + weight-gradient kernels, mlp_bwd2.hip) and of the register-resident
 // training forward that writes its workspace (mlp.hip): width-64 heads with one or four hidden layers and <= 4 outputs -- the
 // reference's sigma / colour decoders.  Everything else (Vanilla 256 x 9, Cobafa 128 x 6, odd shapes) takes the
@@ -198,7 +288,7 @@ inline bool two_pass_supported(const tn_mlp_desc *d) {
     const int extra = extra_rows(d->encoding, d->in_dim, K0_pad);
     const int xs = x_slots(d->encoding, d->in_dim);
     if (xs > 0 && (d->in_dim & 3)) return false;
-    const int R = stash_rows_w(H, L - 1, extra);
+    const int R = StashTile(H, L - 1, extra).rows_w();
     const int aw = d->encoding == TN_ENC_AUX_CAT ? K0_pad - d->in_dim : 0;
     if (R * 8 + (xs > 0 ? 8 * d->in_dim : 0) > 10 * 1024) return false;      // prefetch registers of the wgrad kernel
     if (((size_t)R * 36 + (xs > 0 ? 32 * (size_t)d->in_dim : 0) + 32 * (size_t)aw) * 4 > 160 * 1024 || aw > 64) return false;
@@ -255,6 +345,20 @@ int launch(void (*kern)(P...), int waves, size_t lds, int64_t blocks, hipStream_
     return launch(kern, waves, lds, dim3((unsigned)blocks), s, what, args...);
 }
 
+// where stage_weights puts the layers of `a` (n_layers, K0_pad, out_dim set): [rows][K_pad + 4] + bias per layer
+inline void lay_out_lds(MlpArgs &a, int H)
+{
+    int off = 0;
+    for (int l = 0; l < a.n_layers; ++l) {
+        const int Kp = l == 0 ? a.K0_pad : H;
+        const int rows = (l == a.n_layers - 1) ? (a.out_dim <= 4 ? a.out_dim : ((a.out_dim + 31) & ~31)) : H;
+        a.stride[l] = Kp + 4;
+        a.w_off[l] = off; off += rows * a.stride[l];
+        a.b_off[l] = off; off += (rows + 3) & ~3;
+    }
+    a.lds_floats = off;
+}
+
 inline int plan(const tn_mlp_desc *d, MlpArgs &a, int &H)
 {
     TN_REQUIRE(d, TN_E_NULL, "mlp: null descriptor");
@@ -297,17 +401,11 @@ inline int plan(const tn_mlp_desc *d, MlpArgs &a, int &H)
         break;
     default: return tn::fail(TN_E_CONFIG, "mlp: unknown encoding");
     }
-    int off = 0;
     for (int l = 0; l < L; ++l) {
         a.W[l] = d->weights[l]; a.B[l] = d->biases[l];
         a.K[l] = d->dims[l]; a.N[l] = d->dims[l + 1];
-        const int Kp = l == 0 ? a.K0_pad : H;
-        const int rows = (l == L - 1) ? (a.out_dim <= 4 ? a.out_dim : ((a.out_dim + 31) & ~31)) : H;
-        a.stride[l] = Kp + 4;
-        a.w_off[l] = off; off += rows * a.stride[l];
-        a.b_off[l] = off; off += (rows + 3) & ~3;
     }
-    a.lds_floats = off;
+    lay_out_lds(a, H);
     return TN_OK;
 }
 

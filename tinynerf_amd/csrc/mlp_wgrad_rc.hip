@@ -27,6 +27,7 @@
 #include "mlp_stage.h"
 #include "mlp_f2_heads.h"
 #include "b3_device.h"
+#include "phase_timers.h"
 #include <algorithm>
 
 // phase boundaries of wgrad_rc_kernel's tile loop.  Scheduling barriers there cost 15 spilled registers and left 200-instruction VALU blocks
@@ -35,19 +36,9 @@
 #ifndef TN_RC_SB
 #define TN_RC_SB
 #endif
-#ifdef TN_PHASE_TIMERS            // dev build: where a tile's cycles go (scripts/phase_time_rc.py)
-__device__ unsigned long long tn_phase_cycles_rc[16];
-#define TN_PTR_BEGIN unsigned long long ptr_ = __builtin_amdgcn_s_memtime();
-#define TN_PTR(k) { __builtin_amdgcn_sched_barrier(0); const unsigned long long n_ = __builtin_amdgcn_s_memtime(); if (tn::lane_id() == 0) atomicAdd(&tn_phase_cycles_rc[k], n_ - ptr_); ptr_ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); }
-extern "C" int tn_debug_phase_cycles_rc(unsigned long long *out, int reset) {
-    hipMemcpyFromSymbol(out, HIP_SYMBOL(tn_phase_cycles_rc), sizeof(unsigned long long) * 16);
-    if (reset) { unsigned long long z[16] = {}; hipMemcpyToSymbol(HIP_SYMBOL(tn_phase_cycles_rc), z, sizeof(z)); }
-    return 0;
-}
-#else
-#define TN_PTR_BEGIN
-#define TN_PTR(k)
-#endif
+TN_PHASE_COUNTERS(tn_phase_cycles_rc, tn_debug_phase_cycles_rc)            // (scripts/phase_time_rc.py)
+#define TN_PTR_BEGIN TN_PHASE_BEGIN(ptr_)
+#define TN_PTR(k) TN_PHASE(tn_phase_cycles_rc, ptr_, k)
 namespace {
 
 using tn::f32x16;
@@ -127,13 +118,6 @@ __device__ __forceinline__ void mma_sf(const WOp &w, const u32x4h &bh, const u32
     accF[1] = mfma_f16(bh, w.a1h, accF[1]);
 }
 
-__device__ __forceinline__ void zero2(f32x16 (&a)[2]) {
-#pragma unroll
-    for (int ob = 0; ob < 2; ++ob)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) a[ob][r] = 0.0f;
-}
-
 struct RcArgs {
     MlpArgs a, b;                 // colour head (5 layers) and sigma head (2 layers) in their f16x2 LDS form (plan_f2)
     const float *x, *aux;         // feature rows [n, 96]; per-ray table of TN_ENC_AUX_CAT
@@ -162,7 +146,7 @@ __device__ __forceinline__ void wgrad_rc_body(const RcArgs &p, const float *__re
     const int lane = tn::lane_id(), j_ = lane & 31, h_ = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int64_t n = p.n, n_tiles = (n + 31) >> 5;
-    const int Rta = stash_rows(H, NH, 0), Rtb = stash_rows(H, 1, 0);
+    const int Rta = StashTile(H, NH, 0).rows(), Rtb = StashTile(H, 1, 0).rows();
     constexpr int nga = NGA, nba = NBA;
     constexpr bool has_aux = AUX;
 
@@ -232,7 +216,7 @@ __device__ __forceinline__ void wgrad_rc_body(const RcArgs &p, const float *__re
             WOp w = load_w(W0, plane0, st0, j, h, 6);
             float m = 0.0f;
 #pragma unroll
-            for (int g = 0; g < 8; ++g) m = fmaxf(fmaxf(m, fmaxf(fabsf(av[g][0]), fabsf(av[g][1]))), fmaxf(fabsf(av[g][2]), fabsf(av[g][3])));
+            for (int g = 0; g < 8; ++g) m = tn::max_abs4(m, av[g]);
             float s_a, inv_a;
             f2_scales(wave_max(m), s_a, inv_a);
 #pragma unroll
@@ -252,7 +236,7 @@ __device__ __forceinline__ void wgrad_rc_body(const RcArgs &p, const float *__re
                 for (int r = 0; r < 16; ++r) { actS[ob][r] = accS[ob][r] * ca; actF[ob][r] = accF[ob][r] * ca; }
             }
         } else {
-            zero2(actS); zero2(actF);
+            tn::zero_tiles(actS); tn::zero_tiles(actF);
         }
         TN_RC_SB
         TN_PTR(0)
@@ -262,7 +246,7 @@ __device__ __forceinline__ void wgrad_rc_body(const RcArgs &p, const float *__re
         {
             float m = 0.0f;
 #pragma unroll
-            for (int g = 0; g < 12; ++g) m = fmaxf(fmaxf(m, fmaxf(fabsf(fr[g][0]), fabsf(fr[g][1]))), fmaxf(fabsf(fr[g][2]), fabsf(fr[g][3])));
+            for (int g = 0; g < 12; ++g) m = tn::max_abs4(m, fr[g]);
             float s_x;
             f2_scales(wave_max(m), s_x, inv_x);
 #pragma unroll
@@ -717,7 +701,7 @@ extern "C" int tn_mlp_wgrad_lean_pair(const tn_mlp_desc *desc, const tn_mlp_desc
     f.x = x; f.aux = aux; f.aux_index = p.a.aux_index; f.aux_stride = p.a.aux_stride;
     f.pe = p.a.K0 - p.a.in_dim;
     f.ws_a = ws_a; f.ws_b = ws_b;
-    f.rt_a = stash_rows(H, NH, 0); f.rt_b = stash_rows(H, 1, 0);
+    f.rt_a = StashTile(H, NH, 0).rows(); f.rt_b = StashTile(H, 1, 0).rows();
     f.g0_a = NH * H; f.g0_b = H;
     f.K0_a = p.a.K0; f.K0_b = p.b.K0;
     f.gW0 = gw[0]; f.gB0 = gb[0]; f.gW0s = gws[0]; f.gB0s = gbs[0];
