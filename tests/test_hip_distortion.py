@@ -305,7 +305,7 @@ def _trainer(**kw):
 
 
 def test_distortion_weight_zero_is_the_plain_step(monkeypatch):
-    """no t buffer, the launches of a trainer that never heard of the option with the same sizes and scalars, and the same parameters
+    """no t buffer (the pack's t_values argument is NULL), the launches of a trainer that never heard of the option with the same sizes and scalars, and the same parameters
     after a step -- as far as a TrainConfig() trainer reproduces ITSELF: the plane scatter and the weight-gradient tiles add with fp32
     atomics in whatever order the waves arrive, so two identical trainers already differ after one step (measured on an MI355X:
     3.7e-9 = 2^-28 = 4 ulp of the learning rate on most tensors, 0 or 9e-10 on the two one-element biases, from run to run).  What
@@ -315,26 +315,32 @@ def test_distortion_weight_zero_is_the_plain_step(monkeypatch):
     from tinynerf_amd import _lib as L
     from tinynerf_amd.run import TrainConfig
     assert TrainConfig().distortion_weight == 0.0
-    calls = []
+    calls, pack_t = [], []
     orig = L.call
 
     def record(name, *args):
+        if name == "tn_sample_pack_t":
+            pack_t.append(args[11].value)                    # t_values: behind dev, desc, o, d, R, maskbits, info, base, packed, ray_ids, steps
         calls.append((name,) + tuple(x.value for x in args if isinstance(x, (C.c_int, C.c_int32, C.c_int64, C.c_float))))
         return orig(name, *args)
     monkeypatch.setattr(L, "call", record)
-    seqs, trainers = [], []
+    seqs, trainers, ts = [], [], []
     for kw in ({}, {}, {"distortion_weight": 0.0}, {"distortion_weight": 0.01}):
         tr = _trainer(**kw)
-        del calls[:]
+        del calls[:], pack_t[:]
         tr.step()
         seqs.append(list(calls))
+        ts.append(list(pack_t))
         trainers.append(tr)
     a, a2, b, c = trainers
     assert seqs[0] == seqs[1] == seqs[2]                     # entry points, sizes and scalar arguments
     seqs = [[call[0] for call in seq] for seq in seqs[1:]]
-    assert not any(n in seqs[1] for n in ("tn_sample_pack_t", "tn_distortion_fwd", "tn_distortion_bwd", "tn_render_rays_bwd_dw"))
-    assert all(n in seqs[2] for n in ("tn_sample_pack_t", "tn_distortion_fwd", "tn_distortion_bwd", "tn_render_rays_bwd_dw"))
-    assert len(seqs[2]) == len(seqs[1]) + 2 and "tn_render_rays_bwd" not in seqs[2] and "tn_sample_pack" not in seqs[2]
+    assert not any(n in seqs[1] for n in ("tn_distortion_fwd", "tn_distortion_bwd", "tn_render_rays_bwd_dw"))
+    assert all(n in seqs[2] for n in ("tn_distortion_fwd", "tn_distortion_bwd", "tn_render_rays_bwd_dw"))
+    assert len(seqs[2]) == len(seqs[1]) + 2 and "tn_render_rays_bwd" not in seqs[2]
+    # every pack goes through the one entry point; only the trainer with the loss hands it a t buffer
+    assert all("tn_sample_pack_t" in seq and "tn_sample_pack" not in seq for seq in seqs)
+    assert set(ts[0]) == set(ts[1]) == set(ts[2]) == {None} and set(ts[3]) == {c._arena["t_values"].data_ptr()}
     assert "t_values" not in b._arena and b._batch_t is None and "t_values" in c._arena
     lr_ulp = float(np.spacing(np.float32(1e-2)))
     for (name, p), p2, q in zip(a.renderer.named_parameters(), a2.renderer.parameters(), b.renderer.parameters()):

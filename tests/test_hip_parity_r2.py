@@ -405,21 +405,46 @@ def test_batch_plan_vs_oracle_random(seed):
     np.testing.assert_array_equal(info.cpu().numpy(), np.stack([np.cumsum(flat) - flat, flat], -1).astype(np.int32))
 
 
-@pytest.mark.parametrize("n_rays,B", [(1, 1), (4097, 1024), (50_000, 1024), (49_999, 5000), (300 * 64, 64), (260 * 16 + 3, 16)])
-def test_batch_plan_scan_shapes(n_rays, B):
-    """ragged last batch, batches larger than one 4096-ray sweep, and the > 256-batch fallback to the two single launches"""
-    from tinynerf_amd import _lib as L
+def batch_rule(counts, B, target):
+    """run.py:215-244 restated: (batches taken, their samples, their rays, whether the projection reached the target)"""
+    sums = np.add.reduceat(counts.astype(np.int64), np.arange(0, len(counts), B))
+    cur = k = tripped = 0
+    while k < len(sums) and not tripped:
+        cur += int(sums[k])
+        k += 1
+        tripped = int(int(float(cur) * (1.0 + 1.0 / k)) >= target)
+    return [k, cur, min(k * B, len(counts)), tripped]
+
+
+def batch_plan_cases(n_rays, B):
+    """the counts of test_batch_plan_scan_shapes and its three targets, each with the plan the rule gives: tripping part way, on
+    the last batch (T is the projection there), and not at all (T + 1)"""
     rng = np.random.default_rng(n_rays)
     counts = (rng.integers(0, 200, n_rays) * (rng.random(n_rays) < 0.4)).astype(np.int32)
-    target = int(counts.sum() * 0.6) + 1
+    total, n_batches = int(counts.sum()), -(-n_rays // B)
+    T = int(float(total) * (1.0 + 1.0 / n_batches))
+    cases = [(t, batch_rule(counts, B, t)) for t in (int(total * 0.6) + 1, T, T + 1)]
+    if (n_rays, B) in ((50_000, 1024), (49_999, 5000), (260 * 16 + 3, 16)):              # the ragged clamp R = n_rays < k B
+        assert n_rays < n_batches * B
+        assert cases[1][1] == [n_batches, total, n_rays, 1] and cases[2][1] == [n_batches, total, n_rays, 0]
+    return counts, cases
+
+
+@pytest.mark.parametrize("n_rays,B", [(1, 1), (4097, 1024), (50_000, 1024), (49_999, 5000), (300 * 64, 64), (260 * 16 + 3, 16)])
+def test_batch_plan_scan_shapes(n_rays, B):
+    """ragged last batch, batches larger than one 4096-ray sweep, and the > 256-batch fallback to the two single launches; both
+    entry points against the rule restated in numpy (the two kernels share the rule's code: their agreeing proves nothing)"""
+    from tinynerf_amd import _lib as L
+    counts, cases = batch_plan_cases(n_rays, B)
     c_dev = cu(counts, torch.int32)
-    plan, plan2 = torch.zeros(4, dtype=torch.int32, device=DEV), torch.zeros(4, dtype=torch.int32, device=DEV)
-    info = torch.full((n_rays, 2), -1, dtype=torch.int32, device=DEV)
-    L.call("tn_batch_plan", torch.device(DEV), L.ptr(c_dev), C.c_int64(n_rays), C.c_int32(B), C.c_int64(target), L.ptr(plan))
-    L.call("tn_batch_plan_scan", torch.device(DEV), L.ptr(c_dev), C.c_int64(n_rays), C.c_int32(B), C.c_int64(target), L.ptr(plan2), L.ptr(info))
-    assert plan.tolist() == plan2.tolist()
     flat = counts.astype(np.int64)
-    np.testing.assert_array_equal(info.cpu().numpy(), np.stack([np.cumsum(flat) - flat, flat], -1).astype(np.int32))
+    for target, ref in cases:
+        plan, plan2 = torch.zeros(4, dtype=torch.int32, device=DEV), torch.zeros(4, dtype=torch.int32, device=DEV)
+        info = torch.full((n_rays, 2), -1, dtype=torch.int32, device=DEV)
+        L.call("tn_batch_plan", torch.device(DEV), L.ptr(c_dev), C.c_int64(n_rays), C.c_int32(B), C.c_int64(target), L.ptr(plan))
+        L.call("tn_batch_plan_scan", torch.device(DEV), L.ptr(c_dev), C.c_int64(n_rays), C.c_int32(B), C.c_int64(target), L.ptr(plan2), L.ptr(info))
+        assert plan.tolist() == ref and plan2.tolist() == ref, (target, plan.tolist(), plan2.tolist(), ref)
+        np.testing.assert_array_equal(info.cpu().numpy(), np.stack([np.cumsum(flat) - flat, flat], -1).astype(np.int32))
 
 
 @pytest.mark.parametrize("n_rays", [4096, 4097, 12_345, 640_000, (1 << 21) + 5])

@@ -4,8 +4,8 @@ alone in tests/test_sampler_cases.py).  Floats are compared on their bits; every
 element the kernel does not write shows.
 
 Which launch and which branch each case reaches:
-A. test_pair_vs_oracle[marcher-contraction-box-S]: all six instantiations of sample_mask_kernel / sample_pack_kernel (TN_DISPATCH_MC
-   keys 0..5), on the non-cubic (12, 20, 16) grid, with box ``mixed`` (pow2 == 0: ``/ (hi - lo)``; one axis of it IS a power of two)
+A. test_pair_vs_oracle[marcher-contraction-box-S]: all six instantiations of sample_mask_kernel / sample_pack_kernel (with_pair:
+   marcher 0..1 x contraction 0..2), on the non-cubic (12, 20, 16) grid, with box ``mixed`` (pow2 == 0: ``/ (hi - lo)``; one axis of it IS a power of two)
    and box ``pow2`` (``* inv_ext``).  S = 1 (one lane of one chunk), 63, 64 (a full chunk), 65 (a second chunk of one lane), 200 (four
    chunks, the last partial).  Three modes: training=False (``a.jitter == nullptr && !a.use_rng``; for (aabb, aabb) the exit shortcut is
    on), an explicit jitter table (shortcut off), the device RNG (``a.use_rng``, shortcut on: the production path; counters r * S + k) --

@@ -336,13 +336,9 @@ class RayProvider:
         n = int(total.item())                      # the one host sync: the output shape
         packed = torch.empty((n, 7), device=dev)
         ray_ids = torch.empty(n, dtype=torch.int32, device=dev) if return_ray_ids else None
-        if return_t:
-            t = torch.empty(n, device=dev)
-            L.call("tn_sample_pack_t", dev, C.byref(desc), L.ptr(o), L.ptr(d), C.c_int64(R), L.ptr(maskbits), L.ptr(info),
-                   C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), C.c_void_p(None), L.ptr(t), C.c_int64(n))
-        else:
-            L.call("tn_sample_pack", dev, C.byref(desc), L.ptr(o), L.ptr(d), C.c_int64(R), L.ptr(maskbits), L.ptr(info),
-                   C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), C.c_void_p(None), C.c_int64(n))
+        t = torch.empty(n, device=dev) if return_t else None
+        L.call("tn_sample_pack_t", dev, C.byref(desc), L.ptr(o), L.ptr(d), C.c_int64(R), L.ptr(maskbits), L.ptr(info),
+               C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), C.c_void_p(None), L.ptr(t), C.c_int64(n))
         out = (packed, info) + ((ray_ids,) if return_ray_ids else ()) + ((t,) if return_t else ())
         return out
 

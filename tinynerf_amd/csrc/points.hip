@@ -78,12 +78,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void points_scan_kernel(int64_t *__re
     for (int64_t base = 0; base < n_groups; base += SCAN_THREADS) {       // (trip count uniform over the workgroup)
         const int64_t i = base + tid;
         const int v = i < n_groups ? (int)group[i] : 0;
-        int s = v;                                                       // inclusive scan inside the wave
-#pragma unroll
-        for (int o = 1; o < TN_WAVE; o <<= 1) {
-            const int t = __shfl_up(s, o, TN_WAVE);
-            if (lane >= o) s += t;
-        }
+        const int s = tn::wave_scan(v);
         if (lane == TN_WAVE - 1) wave_total[wave] = s;
         __syncthreads();
         int before = 0, total = 0;

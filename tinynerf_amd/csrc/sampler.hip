@@ -20,6 +20,7 @@
 // one rounded add each.
 #include "tn_common.h"
 #include <math.h>
+#include <type_traits>
 
 namespace {
 
@@ -36,16 +37,25 @@ struct SamplerArgs {
     const float *coarse;      // block maxima (4^3 voxels + 1 halo) or nullptr
     float inv_ext[3];         // pow2: 1 / (hi - lo) per axis, exact
     int pow2;                 // every box extent is a power of two: x / ext == x * inv_ext bit for bit (both are the correctly
-};                            // rounded value of the same real number), and the 12-instruction IEEE division drops out
+                              // rounded value of the same real number), and the 12-instruction IEEE division drops out
+    __device__ int n_chunks() const { return (n_samples + 63) >> 6; }      // 64 candidates, one mask word, per chunk
+};
+
+// ATen's grid_sampler_unnormalize (align_corners=True) of one normalised coordinate and the floor of the result.  trilinear and
+// surely_empty both take the corner from here: the exactness of the coarse reject rests on the two seeing the same x0, y0, z0.
+__device__ __forceinline__ float unnormalise(float x, int size, float &x0)
+{
+    const float ix = ((x + 1.0f) / 2.0f) * (float)(size - 1);
+    x0 = floorf(ix);
+    return ix;
+}
 
 // ATen grid_sampler_3d forward for one point (bilinear, zeros padding, align_corners=True)
 __device__ __forceinline__ float trilinear(const float *__restrict__ grid, int D, int H, int W,
                                            float x, float y, float z)
 {
-    const float ix = ((x + 1.0f) / 2.0f) * (float)(W - 1);
-    const float iy = ((y + 1.0f) / 2.0f) * (float)(H - 1);
-    const float iz = ((z + 1.0f) / 2.0f) * (float)(D - 1);
-    const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
+    float x0, y0, z0;
+    const float ix = unnormalise(x, W, x0), iy = unnormalise(y, H, y0), iz = unnormalise(z, D, z0);
     const float x1 = x0 + 1.0f, y1 = y0 + 1.0f, z1 = z0 + 1.0f;
     const float wx0 = x1 - ix, wx1 = ix - x0;
     const float wy0 = y1 - iy, wy1 = iy - y0;
@@ -77,10 +87,8 @@ __device__ __forceinline__ float trilinear(const float *__restrict__ grid, int D
 // exact lookup runs.  The mask is therefore identical, bit for bit, with and without the coarse grid.
 __device__ __forceinline__ bool surely_empty(const SamplerArgs &a, float x, float y, float z)
 {
-    const float ix = ((x + 1.0f) / 2.0f) * (float)(a.gw - 1);
-    const float iy = ((y + 1.0f) / 2.0f) * (float)(a.gh - 1);
-    const float iz = ((z + 1.0f) / 2.0f) * (float)(a.gd - 1);
-    const float x0 = floorf(ix), y0 = floorf(iy), z0 = floorf(iz);
+    float x0, y0, z0;
+    unnormalise(x, a.gw, x0); unnormalise(y, a.gh, y0); unnormalise(z, a.gd, z0);
     // all taps of an axis out of bounds (or NaN): the exact lookup returns 0, and 0 > threshold is false for threshold >= 0
     const bool inx = x0 >= -1.0f && x0 < (float)a.gw, iny = y0 >= -1.0f && y0 < (float)a.gh, inz = z0 >= -1.0f && z0 < (float)a.gd;
     if (!(inx && iny && inz)) return a.threshold >= 0.0f;
@@ -89,20 +97,37 @@ __device__ __forceinline__ bool surely_empty(const SamplerArgs &a, float x, floa
     return a.coarse[((int64_t)bz * ch + by) * cw + bx] < a.threshold * 0.999f;
 }
 
+// ray parameters at which the ray meets the two faces of the box across axis c (reference core.py:78-79)
+__device__ __forceinline__ void slab(const SamplerArgs &a, const float o[3], const float d[3], int c, float &tl, float &th)
+{
+    const float den = (d[c] == 0.0f) ? (d[c] + 1e-9f) : d[c];
+    tl = (a.lo[c] - o[c]) / den;
+    th = (a.hi[c] - o[c]) / den;
+}
+
 // per-ray constant of the AABB marcher: slab entry distance (reference core.py:78-81)
 __device__ __forceinline__ float aabb_t_min(const SamplerArgs &a, const float o[3], const float d[3])
 {
     float m[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        const float den = (d[c] == 0.0f) ? (d[c] + 1e-9f) : d[c];
-        const float tl = (a.lo[c] - o[c]) / den;
-        const float th = (a.hi[c] - o[c]) / den;
+        float tl, th;
+        slab(a, o, d, c, tl, th);
         m[c] = fminf(tl, th);
     }
     float t = fmaxf(fmaxf(m[0], m[1]), m[2]);
     t = fminf(fmaxf(t, a.near), a.far);
     return t;
+}
+
+// origin and direction of one ray; returns the marcher's per-ray constant
+template <int MARCH>
+__device__ __forceinline__ float load_ray(const SamplerArgs &a, const float *__restrict__ rays_o, const float *__restrict__ rays_d,
+                                          int64_t ray, float o[3], float d[3])
+{
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { o[i] = rays_o[3 * ray + i]; d[i] = rays_d[3 * ray + i]; }
+    return (MARCH == TN_MARCH_AABB) ? aabb_t_min(a, o, d) : 0.0f;
 }
 
 template <int MARCH>
@@ -170,14 +195,8 @@ __global__ void march_rays_kernel(SamplerArgs a, const float *__restrict__ rays_
     if (i >= n_rays * a.n_samples) return;
     const int64_t ray = i / a.n_samples;
     const int k = (int)(i % a.n_samples);
-    float t_min = 0.0f;
-    if constexpr (MARCH == TN_MARCH_AABB) {
-        float o[3], d[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { o[c] = rays_o[3 * ray + c]; d[c] = rays_d[3 * ray + c]; }
-        t_min = aabb_t_min(a, o, d);
-    }
-    float t, delta;
+    float o[3], d[3], t, delta;
+    const float t_min = load_ray<MARCH>(a, rays_o, rays_d, ray, o, d);      // (the unbounded marcher uses neither: the loads drop out)
     march_t<MARCH>(a, t_min, k, t, delta);
     t_values[i] = t;
     step_sizes[i] = delta;
@@ -205,10 +224,8 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void sample_mask_kernel(
     const int64_t ray = (int64_t)blockIdx.x * WAVES_PER_BLOCK + (threadIdx.x >> 6);
     if (ray >= n_rays) return;
     float o[3], d[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { o[i] = rays_o[3 * ray + i]; d[i] = rays_d[3 * ray + i]; }
-    const float t_min = (MARCH == TN_MARCH_AABB) ? aabb_t_min(a, o, d) : 0.0f;
-    const int n_chunks = (a.n_samples + 63) >> 6;
+    const float t_min = load_ray<MARCH>(a, rays_o, rays_d, ray, o, d);
+    const int n_chunks = a.n_chunks();
     // Box marcher + box contraction: behind the ray's exit every candidate fails the in-box test (core.py:29), so the chunks there
     // need no evaluation.  Exact, not approximate: t_k = fl(t_min + fl(k step)) (+ a jitter >= 0) and p_i = fl(o_i + fl(d_i t)) are
     // monotone in k -- rounding is monotone -- so once the UNJITTERED first candidate of a chunk lies beyond a face along an axis the
@@ -220,8 +237,9 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void sample_mask_kernel(
             float t_exit = 3.0e38f;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                const float den = (d[i] == 0.0f) ? (d[i] + 1e-9f) : d[i];
-                t_exit = fminf(t_exit, fmaxf((a.lo[i] - o[i]) / den, (a.hi[i] - o[i]) / den));
+                float tl, th;
+                slab(a, o, d, i, tl, th);
+                t_exit = fminf(t_exit, fmaxf(tl, th));
             }
             const float kf = (t_exit - t_min) / a.step + 2.0f;                  // two steps of slack: the check below decides
             if (kf >= 0.0f && kf < (float)a.n_samples) {
@@ -250,13 +268,63 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void sample_mask_kernel(
         if (lane == 0) maskbits[ray * n_chunks + ch] = m;
         count += __popcll(m);
     }
-    if (n_active + lane < n_chunks) maskbits[ray * n_chunks + n_active + lane] = 0;      // (n_chunks <= 64 for S <= 4096)
+    // the words behind the exit: the first 64 of them in one store (all there are for S <= 4096), the loop takes the rest
+    if (n_active + lane < n_chunks) maskbits[ray * n_chunks + n_active + lane] = 0;
     for (int ch = n_active + 64 + lane; ch < n_chunks; ch += 64) maskbits[ray * n_chunks + ch] = 0;
     if (lane == 0) counts[ray] = count;
 }
 
+// The scan of one tile of 4096 rays by a workgroup of 1024 threads, 4 consecutive rays per thread: rays [tile, tile + 4096) below
+// `end` get (first() + the counts of the tile's rays before them, count).  Returns the tile's counts up to and including this
+// thread's four, so thread 1023 holds the tile's total.  Contains a __syncthreads(): every caller calls it workgroup-uniformly.
+// publish() runs in front of that barrier, behind the loads of the counts (what else the caller hands round through LDS there);
+// first() is evaluated behind it, so it may read what the workgroup wrote to LDS before.  wave_tot (16 words of LDS) is read
+// behind the barrier: a caller that scans a second tile puts a barrier between the two calls.
+template <class Publish, class First>
+__device__ __forceinline__ int32_t scan_tile(const int32_t *__restrict__ counts, int64_t tile, int64_t end, int32_t *wave_tot,
+                                             int32_t *__restrict__ info, Publish publish, First first)
+{
+    const int wave = threadIdx.x >> 6;
+    const int64_t r0 = tile + 4 * (int64_t)threadIdx.x;
+    int32_t c[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) c[u] = (r0 + u < end) ? counts[r0 + u] : 0;
+    const int32_t mine = (c[0] + c[1]) + (c[2] + c[3]);
+    const int32_t v = tn::wave_scan(mine);
+    publish();
+    if (tn::lane_id() == 63) wave_tot[wave] = v;
+    __syncthreads();
+    int32_t wave_off = 0;
+#pragma unroll
+    for (int w = 0; w < 16; ++w) wave_off += w < wave ? wave_tot[w] : 0;
+    int32_t run = first() + wave_off + v - mine;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (r0 + u < end) { info[2 * (r0 + u)] = run; info[2 * (r0 + u) + 1] = c[u]; }
+        run += c[u];
+    }
+    return wave_off + v;
+}
+
+// reference run.py:215-244 -- the dynamic-batch projection rule on the per-loader-batch sums: inherently sequential (<= 4096
+// steps), so ONE lane calls it
+__device__ __forceinline__ void batch_rule(const int32_t *sums, int n_batches, int32_t batch_size, int64_t n_rays, int64_t target,
+                                           int32_t *__restrict__ plan)
+{
+    int64_t cur = 0;
+    int k = 0, tripped = 0;
+    while (k < n_batches) {
+        cur += sums[k];
+        ++k;
+        const int64_t projected = (int64_t)((double)cur * (1.0 + 1.0 / (double)k));     // run.py:240
+        if (projected >= target) { tripped = 1; break; }
+    }
+    const int64_t R = (int64_t)k * batch_size < n_rays ? (int64_t)k * batch_size : n_rays;
+    plan[0] = k; plan[1] = (int32_t)cur; plan[2] = (int32_t)R; plan[3] = tripped;
+}
+
 // Exclusive int32 scan of the per-ray counts (reference core.py:179-181).  One workgroup of 1024
-// threads sweeps the rays in tiles of 4096 (4 consecutive rays per thread) with a running carry: R is
+// threads sweeps the rays in tiles of 4096 (scan_tile) with a running carry: R is
 // 10^3..10^6, the pass moves 12 B/ray; it sits right behind the step's host read-back, so its latency counts.
 __global__ __launch_bounds__(1024) void sample_scan_kernel(
     const int32_t *__restrict__ counts, int64_t n_rays, const int32_t *__restrict__ base_offset,
@@ -264,35 +332,14 @@ __global__ __launch_bounds__(1024) void sample_scan_kernel(
 {
     __shared__ int32_t wave_tot[16];
     __shared__ int32_t carry_s;
-    const int lane = tn::lane_id(), wave = threadIdx.x >> 6;
     const int32_t base = base_offset ? base_offset[0] : 0;
     if (threadIdx.x == 0) carry_s = 0;
     __syncthreads();
     for (int64_t tile = 0; tile < n_rays; tile += 4096) {
-        const int64_t r0 = tile + 4 * (int64_t)threadIdx.x;
-        int32_t c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) c[u] = (r0 + u < n_rays) ? counts[r0 + u] : 0;
-        const int32_t mine = (c[0] + c[1]) + (c[2] + c[3]);
-        int32_t v = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t u = __shfl_up(v, o, 64);
-            if (lane >= o) v += u;
-        }
-        if (lane == 63) wave_tot[wave] = v;
-        __syncthreads();
-        int32_t wave_off = 0;
-        for (int w = 0; w < wave; ++w) wave_off += wave_tot[w];
-        const int32_t carry = carry_s;
-        int32_t run = base + carry + wave_off + v - mine;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (r0 + u < n_rays) { info[2 * (r0 + u)] = run; info[2 * (r0 + u) + 1] = c[u]; }
-            run += c[u];
-        }
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + wave_off + v;
+        int32_t carry;
+        const int32_t upto = scan_tile(counts, tile, n_rays, wave_tot, info, [] {}, [&] { carry = carry_s; return base + carry; });
+        __syncthreads();                                   // every thread has read carry_s and wave_tot
+        if (threadIdx.x == 1023) carry_s = carry + upto;
         __syncthreads();
     }
     if (threadIdx.x == 0 && total) total[0] = carry_s;
@@ -306,37 +353,23 @@ __global__ __launch_bounds__(1024) void sample_scan_mb_kernel(
     int32_t *__restrict__ info, int32_t *__restrict__ total)
 {
     __shared__ int32_t wave_tot[16], pre_tot[16];
-    const int lane = tn::lane_id(), wave = threadIdx.x >> 6;
     const int64_t lo = (int64_t)blockIdx.x * 4096;
     int32_t pre = 0;
     const int4 *c4 = reinterpret_cast<const int4 *>(counts);
     for (int64_t q = threadIdx.x; q < (lo >> 2); q += 1024) { const int4 v = c4[q]; pre += (v.x + v.y) + (v.z + v.w); }
-    const int64_t r0 = lo + 4 * (int64_t)threadIdx.x;
-    int32_t c[4];
+    int32_t below = 0;
+    const int32_t upto = scan_tile(
+        counts, lo, n_rays, wave_tot, info,
+        [&] {
+            pre = tn::wave_sum(pre);
+            if (tn::lane_id() == 0) pre_tot[threadIdx.x >> 6] = pre;
+        },
+        [&] {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) c[u] = (r0 + u < n_rays) ? counts[r0 + u] : 0;
-    const int32_t mine = (c[0] + c[1]) + (c[2] + c[3]);
-    int32_t v = mine;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int32_t u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) pre += __shfl_xor(pre, o, 64);
-    if (lane == 63) wave_tot[wave] = v;
-    if (lane == 0) pre_tot[wave] = pre;
-    __syncthreads();
-    int32_t below = 0, wave_off = 0;
-#pragma unroll
-    for (int w = 0; w < 16; ++w) { below += pre_tot[w]; wave_off += w < wave ? wave_tot[w] : 0; }
-    int32_t run = (base_offset ? base_offset[0] : 0) + below + wave_off + v - mine;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-        if (r0 + u < n_rays) { info[2 * (r0 + u)] = run; info[2 * (r0 + u) + 1] = c[u]; }
-        run += c[u];
-    }
-    if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) total[0] = below + wave_off + v;
+            for (int w = 0; w < 16; ++w) below += pre_tot[w];
+            return (base_offset ? base_offset[0] : 0) + below;
+        });
+    if (total && blockIdx.x == gridDim.x - 1 && threadIdx.x == 1023) total[0] = below + upto;
 }
 
 // Dynamic-batch rule AND the scan of every candidate ray in one launch (tn_batch_plan_scan): workgroup b owns loader batch b.
@@ -351,15 +384,15 @@ __global__ __launch_bounds__(1024) void batch_plan_scan_kernel(const int32_t *__
     __shared__ int32_t sums[MAX_PLAN_BATCHES];
     __shared__ int32_t wave_tot[16];
     __shared__ int32_t carry_s;
-    const int lane = tn::lane_id(), wave = threadIdx.x >> 6;
     const int b = blockIdx.x, n_batches = gridDim.x;
-    for (int j = wave; j < b; j += 16) {
+    // (the sum of a batch over one wave stands here and in batch_plan_kernel: as a helper of the two it cost this launch 0.1 us
+    //  of 8.5, LABNOTES 9.12; the butterfly is tn::wave_sum)
+    for (int j = threadIdx.x >> 6; j < b; j += 16) {
+        const int64_t lo = (int64_t)j * batch_size;
         int32_t s = 0;
-        const int64_t lo = (int64_t)j * batch_size, hi = lo + batch_size;             // j < b: a full batch
-        for (int64_t r = lo + lane; r < hi; r += 64) s += counts[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (lane == 0) sums[j] = s;
+        for (int64_t r = lo + tn::lane_id(); r < lo + batch_size; r += 64) s += counts[r];      // j < b: a full batch
+        s = tn::wave_sum(s);
+        if (tn::lane_id() == 0) sums[j] = s;
     }
     if (threadIdx.x == 0) carry_s = 0;
     __syncthreads();
@@ -368,78 +401,34 @@ __global__ __launch_bounds__(1024) void batch_plan_scan_kernel(const int32_t *__
     const int64_t lo = (int64_t)b * batch_size;
     const int64_t hi = lo + batch_size < n_rays ? lo + batch_size : n_rays;
     for (int64_t tile = lo; tile < hi; tile += 4096) {
-        const int64_t r0 = tile + 4 * (int64_t)threadIdx.x;
-        int32_t c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) c[u] = (r0 + u < hi) ? counts[r0 + u] : 0;
-        const int32_t mine = (c[0] + c[1]) + (c[2] + c[3]);
-        int32_t v = mine;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int32_t u = __shfl_up(v, o, 64);
-            if (lane >= o) v += u;
-        }
-        if (lane == 63) wave_tot[wave] = v;
-        __syncthreads();
-        int32_t wave_off = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) wave_off += w < wave ? wave_tot[w] : 0;
-        const int32_t carry = carry_s;
-        int32_t run = below + carry + wave_off + v - mine;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            if (r0 + u < hi) { info[2 * (r0 + u)] = run; info[2 * (r0 + u) + 1] = c[u]; }
-            run += c[u];
-        }
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + wave_off + v;
+        int32_t carry;
+        const int32_t upto = scan_tile(counts, tile, hi, wave_tot, info, [] {}, [&] { carry = carry_s; return below + carry; });
+        __syncthreads();                                   // every thread has read carry_s and wave_tot
+        if (threadIdx.x == 1023) carry_s = carry + upto;
         __syncthreads();
     }
     if (b == n_batches - 1 && threadIdx.x == 0) {
         sums[b] = carry_s;
-        int64_t cur = 0;
-        int k = 0, tripped = 0;
-        while (k < n_batches) {
-            cur += sums[k];
-            ++k;
-            const int64_t projected = (int64_t)((double)cur * (1.0 + 1.0 / (double)k));     // run.py:240
-            if (projected >= target) { tripped = 1; break; }
-        }
-        const int64_t R = (int64_t)k * batch_size < n_rays ? (int64_t)k * batch_size : n_rays;
-        plan[0] = k; plan[1] = (int32_t)cur; plan[2] = (int32_t)R; plan[3] = tripped;
+        batch_rule(sums, n_batches, batch_size, n_rays, target, plan);
     }
 }
 
-// reference run.py:215-244 -- the dynamic-batch projection rule evaluated on the device: per-loader-batch sums
-// by wave reductions, then the (inherently sequential, <= 4096 steps) rule on one lane.
+// The dynamic-batch rule alone, any number of loader batches up to 4096: per-batch sums by wave reductions, then the rule.
 __global__ __launch_bounds__(1024) void batch_plan_kernel(const int32_t *__restrict__ counts, int64_t n_rays,
                                                           int32_t batch_size, int64_t target, int32_t *__restrict__ plan)
 {
     __shared__ int32_t sums[4096];
-    const int lane = tn::lane_id(), wave = threadIdx.x >> 6;
     const int n_batches = (int)((n_rays + batch_size - 1) / batch_size);
-    for (int b = wave; b < n_batches; b += 16) {
-        int32_t s = 0;
+    for (int b = threadIdx.x >> 6; b < n_batches; b += 16) {
         const int64_t lo = (int64_t)b * batch_size;
         const int64_t hi = lo + batch_size < n_rays ? lo + batch_size : n_rays;
-        for (int64_t r = lo + lane; r < hi; r += 64) s += counts[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if (lane == 0) sums[b] = s;
+        int32_t s = 0;
+        for (int64_t r = lo + tn::lane_id(); r < hi; r += 64) s += counts[r];
+        s = tn::wave_sum(s);
+        if (tn::lane_id() == 0) sums[b] = s;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t cur = 0;
-        int k = 0, tripped = 0;
-        while (k < n_batches) {
-            cur += sums[k];
-            ++k;
-            const int64_t projected = (int64_t)((double)cur * (1.0 + 1.0 / (double)k));     // run.py:240
-            if (projected >= target) { tripped = 1; break; }
-        }
-        const int64_t R = (int64_t)k * batch_size < n_rays ? (int64_t)k * batch_size : n_rays;
-        plan[0] = k; plan[1] = (int32_t)cur; plan[2] = (int32_t)R; plan[3] = tripped;
-    }
+    if (threadIdx.x == 0) batch_rule(sums, n_batches, batch_size, n_rays, target, plan);
 }
 
 template <int MARCH, int CONTRACT>
@@ -456,10 +445,8 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void sample_pack_kernel(
     if (count == 0) return;
     int64_t out = (int64_t)info[2 * ray] - (base_offset ? base_offset[0] : 0);
     float o[3], d[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { o[i] = rays_o[3 * ray + i]; d[i] = rays_d[3 * ray + i]; }
-    const float t_min = (MARCH == TN_MARCH_AABB) ? aabb_t_min(a, o, d) : 0.0f;
-    const int n_chunks = (a.n_samples + 63) >> 6;
+    const float t_min = load_ray<MARCH>(a, rays_o, rays_d, ray, o, d);
+    const int n_chunks = a.n_chunks();
     for (int ch = 0; ch < n_chunks; ++ch) {
         const uint64_t m = maskbits[ray * n_chunks + ch];
         if (m == 0) continue;
@@ -585,19 +572,22 @@ int make_args(const tn_sampler_desc *d, SamplerArgs &a, bool need_grid = true)
 
 inline unsigned ray_blocks(int64_t n_rays) { return (unsigned)((n_rays + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK); }
 
-// compile-time specialisation of the (marcher, contraction) pair: no per-candidate branching
-#define TN_DISPATCH_MC(a, ...)                                                                        \
-    do {                                                                                              \
-        const int key_ = (a).marcher * 3 + (a).contraction;                                           \
-        switch (key_) {                                                                               \
-        case 0: { constexpr int M = 0, Cn = 0; __VA_ARGS__; } break;                                         \
-        case 1: { constexpr int M = 0, Cn = 1; __VA_ARGS__; } break;                                         \
-        case 2: { constexpr int M = 0, Cn = 2; __VA_ARGS__; } break;                                         \
-        case 3: { constexpr int M = 1, Cn = 0; __VA_ARGS__; } break;                                         \
-        case 4: { constexpr int M = 1, Cn = 1; __VA_ARGS__; } break;                                         \
-        default: { constexpr int M = 1, Cn = 2; __VA_ARGS__; } break;                                        \
-        }                                                                                             \
-    } while (0)
+// Compile-time specialisation of the marcher and of the contraction -- no per-candidate branching, and no runtime-selected
+// contraction under -ffp-contract=off (LABNOTES 4.2): f(std::integral_constant<int, v>) for the v in [0, N) that make_args let through.
+template <int N, class F>
+void with_constant(int v, F f)
+{
+    if constexpr (N > 1) {
+        if (v != N - 1) return with_constant<N - 1>(v, f);
+    }
+    f(std::integral_constant<int, N - 1>());
+}
+template <class F> void with_marcher(const SamplerArgs &a, F f) { with_constant<TN_MARCH_UNBOUNDED + 1>(a.marcher, f); }
+template <class F> void with_contraction(const SamplerArgs &a, F f) { with_constant<TN_CONTRACT_MIP360_L2 + 1>(a.contraction, f); }
+template <class F> void with_pair(const SamplerArgs &a, F f)
+{
+    with_marcher(a, [&](auto M) { with_contraction(a, [&](auto Cn) { f(M, Cn); }); });
+}
 
 }  // namespace
 
@@ -610,12 +600,10 @@ extern "C" int tn_march_rays(const tn_sampler_desc *desc, const float *rays_o, c
     if (n_rays == 0) return TN_OK;
     TN_REQUIRE(rays_o && rays_d && t_values && step_sizes, TN_E_NULL, "tn_march_rays: null pointer");
     const int64_t n = n_rays * a.n_samples;
-    if (a.marcher == TN_MARCH_AABB)
-        hipLaunchKernelGGL(march_rays_kernel<TN_MARCH_AABB>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           a, rays_o, rays_d, n_rays, t_values, step_sizes);
-    else
-        hipLaunchKernelGGL(march_rays_kernel<TN_MARCH_UNBOUNDED>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           a, rays_o, rays_d, n_rays, t_values, step_sizes);
+    with_marcher(a, [&](auto M) {
+        march_rays_kernel<M.value><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
+            a, rays_o, rays_d, n_rays, t_values, step_sizes);
+    });
     return tn::check_launch("march_rays_kernel");
 }
 
@@ -627,13 +615,9 @@ extern "C" int tn_contract(const tn_sampler_desc *desc, const float *coords, int
     TN_REQUIRE(n >= 0, TN_E_SIZE, "tn_contract: negative n");
     if (n == 0) return TN_OK;
     TN_REQUIRE(coords && coords_out, TN_E_NULL, "tn_contract: null pointer");
-    const dim3 grid((unsigned)((n + 255) / 256));
-    if (a.contraction == TN_CONTRACT_AABB)
-        hipLaunchKernelGGL(contract_kernel<TN_CONTRACT_AABB>, grid, dim3(256), 0, (hipStream_t)stream, a, coords, n, coords_out, mask);
-    else if (a.contraction == TN_CONTRACT_MIP360_INF)
-        hipLaunchKernelGGL(contract_kernel<TN_CONTRACT_MIP360_INF>, grid, dim3(256), 0, (hipStream_t)stream, a, coords, n, coords_out, mask);
-    else
-        hipLaunchKernelGGL(contract_kernel<TN_CONTRACT_MIP360_L2>, grid, dim3(256), 0, (hipStream_t)stream, a, coords, n, coords_out, mask);
+    with_contraction(a, [&](auto Cn) {
+        contract_kernel<Cn.value><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(a, coords, n, coords_out, mask);
+    });
     return tn::check_launch("contract_kernel");
 }
 
@@ -645,8 +629,10 @@ extern "C" int tn_sample_mask(const tn_sampler_desc *desc, const float *rays_o, 
     TN_REQUIRE(n_rays >= 0, TN_E_SIZE, "tn_sample_mask: negative n_rays");
     if (n_rays == 0) return TN_OK;
     TN_REQUIRE(rays_o && rays_d && maskbits && counts, TN_E_NULL, "tn_sample_mask: null pointer");
-    TN_DISPATCH_MC(a, sample_mask_kernel<M, Cn><<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(
-                          a, rays_o, rays_d, n_rays, maskbits, counts));
+    with_pair(a, [&](auto M, auto Cn) {
+        sample_mask_kernel<M.value, Cn.value><<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(
+            a, rays_o, rays_d, n_rays, maskbits, counts);
+    });
     return tn::check_launch("sample_mask_kernel");
 }
 
@@ -656,11 +642,11 @@ extern "C" int tn_sample_scan(const int32_t *counts, int64_t n_rays, const int32
     TN_REQUIRE(n_rays >= 0, TN_E_SIZE, "tn_sample_scan: negative n_rays");
     TN_REQUIRE(n_rays == 0 || (counts && info), TN_E_NULL, "tn_sample_scan: null pointer");
     if (n_rays > 4096 && n_rays <= ((int64_t)1 << 21) && (reinterpret_cast<uintptr_t>(counts) & 15) == 0) {
-        hipLaunchKernelGGL(sample_scan_mb_kernel, dim3((unsigned)((n_rays + 4095) / 4096)), dim3(1024), 0, (hipStream_t)stream, counts, n_rays,
-                           base_offset, info, total);
+        sample_scan_mb_kernel<<<dim3((unsigned)((n_rays + 4095) / 4096)), dim3(1024), 0, (hipStream_t)stream>>>(
+            counts, n_rays, base_offset, info, total);
         return tn::check_launch("sample_scan_mb_kernel");
     }
-    hipLaunchKernelGGL(sample_scan_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, counts, n_rays, base_offset, info, total);
+    sample_scan_kernel<<<dim3(1), dim3(1024), 0, (hipStream_t)stream>>>(counts, n_rays, base_offset, info, total);
     return tn::check_launch("sample_scan_kernel");
 }
 
@@ -682,7 +668,8 @@ extern "C" int tn_batch_plan_scan(const int32_t *counts, int64_t n_rays, int32_t
     TN_REQUIRE(n_batches <= 4096, TN_E_SIZE, "tn_batch_plan_scan: more than 4096 loader batches");
     TN_REQUIRE(plan && (n_rays == 0 || (counts && info)), TN_E_NULL, "tn_batch_plan_scan: null pointer");
     if (n_batches >= 1 && n_batches <= MAX_PLAN_BATCHES) {
-        batch_plan_scan_kernel<<<dim3((unsigned)n_batches), dim3(1024), 0, (hipStream_t)stream>>>(counts, n_rays, batch_size, target, plan, info);
+        batch_plan_scan_kernel<<<dim3((unsigned)n_batches), dim3(1024), 0, (hipStream_t)stream>>>(
+            counts, n_rays, batch_size, target, plan, info);
         return tn::check_launch("batch_plan_scan_kernel");
     }
     if (int rc = tn_batch_plan(counts, n_rays, batch_size, target, plan, stream)) return rc;
@@ -698,8 +685,10 @@ extern "C" int tn_sample_pack_t(const tn_sampler_desc *desc, const float *rays_o
     TN_REQUIRE(n_rays >= 0 && capacity >= 0, TN_E_SIZE, "tn_sample_pack: negative size");
     if (n_rays == 0 || capacity == 0) return TN_OK;
     TN_REQUIRE(rays_o && rays_d && maskbits && info && packed, TN_E_NULL, "tn_sample_pack: null pointer");
-    TN_DISPATCH_MC(a, sample_pack_kernel<M, Cn><<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(
-                          a, rays_o, rays_d, n_rays, maskbits, info, base_offset, packed, ray_ids, steps, capacity, t_values));
+    with_pair(a, [&](auto M, auto Cn) {
+        sample_pack_kernel<M.value, Cn.value><<<dim3(ray_blocks(n_rays)), dim3(WAVES_PER_BLOCK * 64), 0, (hipStream_t)stream>>>(
+            a, rays_o, rays_d, n_rays, maskbits, info, base_offset, packed, ray_ids, steps, capacity, t_values);
+    });
     return tn::check_launch("sample_pack_kernel");
 }
 
@@ -716,8 +705,8 @@ extern "C" int tn_occupancy_query(const float *grid, int D, int H, int W, const 
     TN_REQUIRE(n >= 0 && D > 0 && H > 0 && W > 0, TN_E_SIZE, "tn_occupancy_query: bad size");
     if (n == 0) return TN_OK;
     TN_REQUIRE(grid && coords && (out || values), TN_E_NULL, "tn_occupancy_query: null pointer");
-    hipLaunchKernelGGL(occupancy_query_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       grid, D, H, W, coords, n, threshold, out, values);
+    occupancy_query_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
+        grid, D, H, W, coords, n, threshold, out, values);
     return tn::check_launch("occupancy_query_kernel");
 }
 
@@ -727,8 +716,8 @@ extern "C" int tn_occupancy_slice_coords(int D, int H, int W, int slice, const f
     TN_REQUIRE(D > 0 && H > 0 && W > 0 && slice >= 0 && slice < D, TN_E_SIZE, "tn_occupancy_slice_coords: bad size");
     TN_REQUIRE(coords, TN_E_NULL, "tn_occupancy_slice_coords: null pointer");
     const int64_t n = (int64_t)H * W;
-    hipLaunchKernelGGL(occupancy_slice_coords_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       D, H, W, slice, jitter, seed, coords);
+    occupancy_slice_coords_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
+        D, H, W, slice, jitter, seed, coords);
     return tn::check_launch("occupancy_slice_coords_kernel");
 }
 
@@ -738,8 +727,8 @@ extern "C" int tn_occupancy_apply(float *grid_cells, const float *sigmas, int64_
     TN_REQUIRE(n >= 0, TN_E_SIZE, "tn_occupancy_apply: negative size");
     if (n == 0) return TN_OK;
     TN_REQUIRE(grid_cells && sigmas, TN_E_NULL, "tn_occupancy_apply: null pointer");
-    hipLaunchKernelGGL(occupancy_apply_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       grid_cells, sigmas, n, step_size, threshold, decay);
+    occupancy_apply_kernel<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream>>>(
+        grid_cells, sigmas, n, step_size, threshold, decay);
     return tn::check_launch("occupancy_apply_kernel");
 }
 
@@ -751,8 +740,7 @@ extern "C" int tn_occupancy_stats(const float *grid, int64_t n, float threshold,
     if (e != hipSuccess) { tn::set_error("tn_occupancy_stats: memset: %s", hipGetErrorString(e)); return (int)e; }
     if (n == 0) return TN_OK;
     const unsigned blocks = (unsigned)((n + 256 * 16 - 1) / (256 * 16));
-    hipLaunchKernelGGL(occupancy_stats_kernel, dim3(blocks > 2048 ? 2048 : blocks), dim3(256), 0, (hipStream_t)stream,
-                       grid, n, threshold, stats);
+    occupancy_stats_kernel<<<dim3(blocks > 2048 ? 2048 : blocks), dim3(256), 0, (hipStream_t)stream>>>(grid, n, threshold, stats);
     return tn::check_launch("occupancy_stats_kernel");
 }
 

@@ -39,6 +39,22 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+__device__ __forceinline__ int32_t wave_sum(int32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// inclusive scan over the lanes of the wave: lane l gets v(0) + ... + v(l)
+__device__ __forceinline__ int32_t wave_scan(int32_t v) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int32_t u = __shfl_up(v, o, 64);
+        if (lane_id() >= o) v += u;
+    }
+    return v;
+}
+
 // counter-based U[0,1): two rounds of a 64-bit mix (splitmix64 finaliser) -> 24 random bits
 __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t ctr) {
     uint64_t z = seed + 0x9E3779B97F4A7C15ull * (ctr + 1);

@@ -409,11 +409,8 @@ class Trainer:
         t = None
         if self.cfg.distortion_weight > 0:        # the distortion loss needs the ray parameter of every sample: the same kernel writes it out
             t = self._buf("t_values", (n,), torch.float32)
-            L.call("tn_sample_pack_t", dev, C.byref(pend["desc"]), L.ptr(pend["o"]), L.ptr(pend["d"]), C.c_int64(R), L.ptr(pend["maskbits"]),
-                   L.ptr(info), C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), L.ptr(steps), L.ptr(t), C.c_int64(n))
-        else:
-            L.call("tn_sample_pack", dev, C.byref(pend["desc"]), L.ptr(pend["o"]), L.ptr(pend["d"]), C.c_int64(R), L.ptr(pend["maskbits"]),
-                   L.ptr(info), C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), L.ptr(steps), C.c_int64(n))
+        L.call("tn_sample_pack_t", dev, C.byref(pend["desc"]), L.ptr(pend["o"]), L.ptr(pend["d"]), C.c_int64(R), L.ptr(pend["maskbits"]),
+               L.ptr(info), C.c_void_p(None), L.ptr(packed), L.ptr(ray_ids), L.ptr(steps), L.ptr(t), C.c_int64(n))
         # what the fused render node would otherwise rebuild from (packed, info): ray id and step of every sample, ray directions
         # "Empty iteration" flag of this step: one slot of a ring that is zeroed once per lap (the weights kernel only raises it)
         slot = self._gate_tick % self._gate_ring.numel()          # (a counter of its own: a batch may be built without a step)
