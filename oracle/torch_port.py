@@ -62,6 +62,43 @@ def cobafa_features(sd: Dict[str, torch.Tensor], x: torch.Tensor, freqs, prefix:
     return mlp(sd, prefix + "mlp.net.", feat)
 
 
+HASH_P1, HASH_P2 = 2654435761, 805459861          # Instant-NGP's primes (the first axis is multiplied by 1)
+
+
+def hashgrid_features(sd: Dict[str, torch.Tensor], x: torch.Tensor, plan, prefix: str = "feature_module.") -> torch.Tensor:
+    """The multiresolution hash grid of include/tinynerf_hip.h / DESIGN 6e (no reference counterpart), differentiable in the table and
+    evaluated in the table's dtype.  ``plan`` = (res, hashed, entries, offsets) as python ints.  Per level of N cells per axis:
+    p = x * N/2 + N/2 formed in float64 and rounded to fp32 ONCE, a NaN goes to 0, p is clamped to [0, N]; i = min(int(p), N - 1),
+    f = p - i; eight corners (bit 0 of the corner number: x), weights prod(f or 1 - f); dense index ix + (N+1)(iy + (N+1) iz), or
+    (ix ^ iy * P1 ^ iz * P2) in 32 bits masked to entries - 1.  -> [n, levels * features], level-major."""
+    table = sd[prefix + "table"]
+    res, hashed, entries, offsets = plan
+    x64 = x.detach().to(torch.float32).to(torch.float64)
+    feats = []
+    for n_l, hsh, ent, off in zip(res, hashed, entries, offsets):
+        h = 0.5 * n_l
+        p = (x64 * h + h).to(torch.float32)
+        p = torch.where(p > 0, p, torch.zeros_like(p))                          # a NaN lands on 0
+        p = torch.where(p < n_l, p, torch.full_like(p, float(n_l)))
+        i = torch.clamp(p.to(torch.int64), max=n_l - 1)
+        f = (p.to(torch.float64) - i).to(table.dtype)
+        vals = []
+        for k in range(8):
+            d = (k & 1, (k >> 1) & 1, k >> 2)
+            w = None
+            for a in range(3):
+                wa = f[:, a] if d[a] else 1.0 - f[:, a]
+                w = wa if w is None else w * wa
+            ix, iy, iz = i[:, 0] + d[0], i[:, 1] + d[1], i[:, 2] + d[2]
+            if hsh:
+                idx = (ix ^ ((iy * HASH_P1) & 0xFFFFFFFF) ^ ((iz * HASH_P2) & 0xFFFFFFFF)) & (ent - 1)
+            else:
+                idx = ix + (n_l + 1) * (iy + (n_l + 1) * iz)
+            vals.append(w[:, None] * table[off + idx])
+        feats.append(torch.stack(vals, 1).sum(1))
+    return torch.cat(feats, -1)
+
+
 def _layers(sd: Dict[str, torch.Tensor], prefix: str):
     keys = sorted({k[len(prefix):].rsplit(".", 1)[0] for k in sd if k.startswith(prefix) and k.endswith(".weight")},
                   key=lambda s: int(s.split(".")[0]))
@@ -153,7 +190,7 @@ class _Weights(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, sigmas, steps, info, thr):
-        w = torch.from_numpy(orc.weights_fwd(sigmas.detach().numpy(), steps.detach().numpy(), info.numpy(), float(thr)))
+        w = torch.from_numpy(orc.weights_fwd(sigmas.detach().numpy(), steps.detach().numpy(), info.numpy(), float(thr))).to(sigmas.dtype)
         ctx.save_for_backward(sigmas, steps, info, w)
         return w
 
@@ -173,11 +210,13 @@ class _Weights(torch.autograd.Function):
             for a, c in info.numpy():
                 scale[a:a + c] = wg[a:a + c].sum() * np.sqrt(max(int(c), 1))
             gs = (gs + d.detach().numpy() * scale * np.float32(2.0 ** -23) * rng.uniform(-1, 1, gs.shape).astype(np.float32)).astype(np.float32)
-        return torch.from_numpy(gs), None, None, None
+        return torch.from_numpy(gs).to(s.dtype), None, None, None
 
 
-def features(sd: Dict[str, torch.Tensor], x: torch.Tensor, vanilla_freqs: int = 0, cobafa_freqs=None) -> torch.Tensor:
-    """the three feature modules of run.py:130-147 behind one call"""
+def features(sd: Dict[str, torch.Tensor], x: torch.Tensor, vanilla_freqs: int = 0, cobafa_freqs=None, hashgrid=None) -> torch.Tensor:
+    """the three feature modules of run.py:130-147 (and the hash grid: ``hashgrid`` = its level plan) behind one call"""
+    if hashgrid is not None:
+        return hashgrid_features(sd, x, hashgrid)
     if cobafa_freqs is not None:
         return cobafa_features(sd, x, cobafa_freqs)
     if vanilla_freqs:
@@ -186,16 +225,16 @@ def features(sd: Dict[str, torch.Tensor], x: torch.Tensor, vanilla_freqs: int = 
 
 
 def render(sd: Dict[str, torch.Tensor], packed: torch.Tensor, info: torch.Tensor, bg: Optional[torch.Tensor],
-           thr: float = 1e-4, vanilla_freqs: int = 0, cobafa_freqs=None) -> torch.Tensor:
-    """core.py:225-267 for a K-Planes (or Vanilla: vanilla_freqs > 0, or Cobafa: cobafa_freqs) field with the Vanilla
-    decoders."""
+           thr: float = 1e-4, vanilla_freqs: int = 0, cobafa_freqs=None, hashgrid=None) -> torch.Tensor:
+    """core.py:225-267 for a K-Planes (or Vanilla: vanilla_freqs > 0, or Cobafa: cobafa_freqs, or hash grid: hashgrid = its level
+    plan) field with the Vanilla decoders."""
     n, R = packed.size(0), info.size(0)
     x = packed[:, :3]
-    feat = features(sd, x, vanilla_freqs, cobafa_freqs)
+    feat = features(sd, x, vanilla_freqs, cobafa_freqs, hashgrid)
     sig = _TruncExp.apply(mlp(sd, "sigma_decoder.net.net.", feat) - 1.).ravel()
     w = _Weights.apply(sig, packed[:, 6].contiguous(), info, thr)
     mask = w > 0
-    rgbs = torch.zeros((n, 3))
+    rgbs = torch.zeros((n, 3), dtype=feat.dtype)          # (fp32 as the reference runs; a float64 state dict and batch render in float64)
     if mask.any():
         d = packed[:, 3:6][mask]
         inp = torch.cat([posenc(d, sd["rgb_decoder.pe.freqs"]), d, feat[mask]], -1)
@@ -205,9 +244,9 @@ def render(sd: Dict[str, torch.Tensor], packed: torch.Tensor, info: torch.Tensor
         rgbs = torch.zeros((n, 3), requires_grad=True)
         w = torch.zeros(n, requires_grad=True)
     idx = torch.repeat_interleave(torch.arange(R), info[:, 1].long())
-    out = torch.zeros((R, 3)).index_add(0, idx, rgbs)
+    out = torch.zeros((R, 3), dtype=rgbs.dtype).index_add(0, idx, rgbs)
     if bg is not None:
-        op = torch.zeros(R).index_add(0, idx, w)
+        op = torch.zeros(R, dtype=w.dtype).index_add(0, idx, w)
         out = out + bg * (1 - op[:, None])
     return out
 
@@ -310,7 +349,7 @@ def reference_training(sd0: Dict[str, torch.Tensor], rays_o: np.ndarray, rays_d:
                        bg=(1.0, 1.0, 1.0), grad_scale: float = 1024.0, vanilla_freqs: int = 10, scene_type: str = "aabb",
                        scene_scale: float = 1.0, cobafa_freqs=None, occ_updates: int = 0, grid0=None, grids_out=None,
                        stochastic_seed: Optional[int] = None, eval_at=(), eval_fn=None, on_step=None, replay: Optional[dict] = None,
-                       lr: float = 1e-2, loader: str = "stream", lrs_out=None):
+                       lr: float = 1e-2, loader: str = "stream", lrs_out=None, hashgrid=None):
     """The reference's train() loop (run.py:97-319) on CPU in deterministic form: consecutive rays instead of a
     shuffled loader, no sampling jitter, voxel-centre occupancy refresh.  Literals as in run.py:100-114,186-202,
     including the scaled-and-never-unscaled loss.  Returns (losses, final state dict, per-step sample counts).
@@ -333,7 +372,11 @@ def reference_training(sd0: Dict[str, torch.Tensor], rays_o: np.ndarray, rays_d:
     ``loader="dataloader"`` (round 6, with ``replay``): the permutations are walked as ``DataLoader(shuffle=True)`` walks them
     (run.py:116-122,221-225) -- the partial last batch of an epoch is handed out as it is and the next epoch starts with a fresh
     permutation -- which is how ``oracle/make_train_trace.py`` drives the reference's own ``train()``: golden G22 holds this function
-    to that run (tests/test_oracle_train_trace.py).  ``lrs_out`` (a list) receives the learning rate after every ``scheduler.step()``."""
+    to that run (tests/test_oracle_train_trace.py).  ``lrs_out`` (a list) receives the learning rate after every ``scheduler.step()``.
+    ``hashgrid`` (a level plan, with ``method="hashgrid"``): the field is ``hashgrid_features`` over ``feature_module.table``; the loss is
+    the plain MSE without a regulariser, as tinynerf_amd/run.py Trainer has it for this method (no reference counterpart)."""
+    if (method == "hashgrid") != (hashgrid is not None):
+        raise ValueError("method='hashgrid' and the hashgrid= level plan go together")
     sd = {k: (v.detach().clone().requires_grad_(True) if v.is_floating_point() and not k.endswith("freqs") else v.clone())
           for k, v in sd0.items()}
     params = [v for v in sd.values() if v.requires_grad]
@@ -391,7 +434,7 @@ def reference_training(sd0: Dict[str, torch.Tensor], rays_o: np.ndarray, rays_d:
     def sigma_np(pts: np.ndarray) -> np.ndarray:
         with torch.no_grad():
             x = torch.from_numpy(np.ascontiguousarray(pts))
-            feat = features(sd, x, vf, cf)
+            feat = features(sd, x, vf, cf, hashgrid)
             return torch.exp(mlp(sd, "sigma_decoder.net.net.", feat) - 1.).numpy()
 
     for step in range(n_steps):
@@ -439,7 +482,7 @@ def reference_training(sd0: Dict[str, torch.Tensor], rays_o: np.ndarray, rays_d:
                 grids_out.append((step, grid.copy(), mean))
         if on_step is not None:
             on_step(step, sd, packed, info, target)
-        out = render(sd, torch.from_numpy(packed), torch.from_numpy(info), bg_t, vanilla_freqs=vf, cobafa_freqs=cf)
+        out = render(sd, torch.from_numpy(packed), torch.from_numpy(info), bg_t, vanilla_freqs=vf, cobafa_freqs=cf, hashgrid=hashgrid)
         loss = torch.nn.functional.mse_loss(out, torch.from_numpy(target))
         if method == "kplanes":
             loss = loss + 1e-4 * loss_tv(sd)

@@ -36,7 +36,7 @@ def _matches(got, ref, keys, rel) -> bool:
 
 def assert_grads_match_up_to_relu_ties(got: Dict[str, np.ndarray], compute_ref: Callable[[], Dict[str, np.ndarray]], rel,
                                        eps: float = 2e-6, max_flips: int = 256, weights_conditioning: bool = False,
-                                       golden: Dict[str, np.ndarray] = None, cond_cap: float = None) -> int:
+                                       golden: Dict[str, np.ndarray] = None, cond_cap: float = None, matched: dict = None) -> int:
     """``compute_ref()`` evaluates the reference gradients through oracle/torch_port.mlp (on any device) and returns
     {name: array}.  |got - ref| <= rel * max|ref| per tensor (``rel``: one number or {name: number}) for some assignment of the tie units (|pre| <= eps * sum |terms|;
     the rounding error of an fp32 dot product of K <= 307 terms is ~sqrt(K) * 6e-8 = 1e-6 of that sum).  Returns the number of
@@ -44,7 +44,9 @@ def assert_grads_match_up_to_relu_ties(got: Dict[str, np.ndarray], compute_ref: 
     ``golden`` {name: gradient captured from the reference itself}: when no tie unit had to be flipped, `got` is ALSO compared
     with it directly, same tolerance -- the reference stays the oracle, the port only supplies the tie bookkeeping.
     ``cond_cap``: upper bound on any conditioning-derived tolerance (a fixture whose reference gradients are looser than this
-    pins nothing and must be replaced)."""
+    pins nothing and must be replaced).
+    ``matched`` (a dict): receives the reference gradients `got` was finally held to (tie units in their accepted states) and, under
+    the key "rel", the tolerances used -- for callers that report how much of the allowance was used."""
     if weights_conditioning:
         # render-level fixtures: the reference's fp32 weights backward (cuda.cu:49-56) is itself only this close to an exact
         # evaluation of its formula (oracle/torch_port.weights_conditioning); no other fp32 order can be held to less
@@ -66,6 +68,8 @@ def assert_grads_match_up_to_relu_ties(got: Dict[str, np.ndarray], compute_ref: 
         if golden is not None:
             _check(got, golden, keys, {k: tol(k, base) / max(float(np.abs(np.asarray(golden[k])).max()), 1e-30) for k in keys},
                    "directly against the reference's golden gradients")
+        if matched is not None:
+            matched.update(base, rel={k: tol(k, base) / max(float(np.abs(np.asarray(base[k])).max()), 1e-30) for k in keys})
         return 0
     def dist2(ref):          # squared distance in units of the tolerances: every correct flip lowers it, whatever the others do
         return sum(float((((np.asarray(got[k], np.float64) - np.asarray(ref[k], np.float64)) / tol(k, base)) ** 2).sum()) for k in keys)
@@ -85,4 +89,6 @@ def assert_grads_match_up_to_relu_ties(got: Dict[str, np.ndarray], compute_ref: 
             cur = compute_ref()
     _check(got, cur, keys, {k: tol(k, base) / max(float(np.abs(np.asarray(cur[k])).max()), 1e-30) for k in keys},
            f"{len(flips)} of {len(ties)} tie units flipped: {sorted(flips)}")
+    if matched is not None:
+        matched.update(cur, rel={k: tol(k, base) / max(float(np.abs(np.asarray(cur[k])).max()), 1e-30) for k in keys})
     return len(flips)

@@ -174,9 +174,8 @@ def test_no_samples():
     assert fm.table.grad is not None and float(fm.table.grad.abs().max()) == 0.0
 
 
-def test_renderer_takes_the_fused_node_and_equals_the_module_path():
+def _renderer_and_batch():
     import _g22
-    from tinynerf_amd import fused
     from tinynerf_amd.run import TrainConfig, build_renderer
     o, d, _, bg = _g22.ray_table()
     cfg = TrainConfig(method="hashgrid", n_samples=64, occupancy_res=32, hashgrid_log2_table_size=14)
@@ -186,6 +185,12 @@ def test_renderer_takes_the_fused_node_and_equals_the_module_path():
         renderer.feature_module.table.uniform_(-1, 1)                     # (the initialisation's 1e-4 would make every feature ~ 0)
     idx = np.arange(0, 80000, 263)[:300]
     packed, info = provider(torch.from_numpy(o[idx]).to(DEV), torch.from_numpy(d[idx]).to(DEV), training=False)
+    return renderer, packed, info, bg
+
+
+def test_renderer_takes_the_fused_node_and_equals_the_module_path():
+    from tinynerf_amd import fused
+    renderer, packed, info, _ = _renderer_and_batch()
     assert fused.supports(renderer) and packed.size(0) > 3000
     with torch.no_grad():
         a = renderer(packed, info)
@@ -195,3 +200,130 @@ def test_renderer_takes_the_fused_node_and_equals_the_module_path():
     err = float((a - b).abs().max())
     print(f"fused against module path on {packed.size(0)} samples: max difference {err:.3e}")
     assert err <= TOL and float(a.std()) > 1e-3
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Backward of the render paths in front of a hash-grid field (fused._RenderHeads without a row-view link: 32-wide features, the colour
+# head as TN_ENC_DIR_CAT with per-sample directions, the unpaired heads backward with TN_MLP_ACCUM_GRAD_X on the sigma head, a real
+# d loss / d feat handed back to autograd, tn_hashgrid_bwd behind it) and of the module-by-module path, each against the CPU port
+# evaluated in float64 on the same packed batch (oracle/torch_port.render with a float64 state dict: hash grid, both heads and the
+# composite in float64; the weights scan stays the reference kernels' fp32 C restatement, whose conditioning the comparison allows
+# for as everywhere else).  Rule: tests/_ties.assert_grads_match_up_to_relu_ties at 1e-4 of each tensor's largest element, the table
+# as sixteen tensors, one per level.  Each path is bound against the port, not the two paths against each other.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _cut_into_rays(n, seed):
+    """packing info that cuts n ray-ordered samples anew so that rays END at lanes 0, 31, 32 and 63 of a wave (counts 1, 31, 1, 31
+    from sample 0), rays of a single sample exist, and the rest are 1 .. 256 samples long"""
+    rng = np.random.default_rng(seed)
+    cnt = [1, 31, 1, 31]
+    while sum(cnt) < n:
+        cnt.append(int(rng.integers(1, 257)))
+    cnt[-1] -= sum(cnt) - n
+    cnt = np.array(cnt, np.int32)
+    info = np.stack([np.cumsum(cnt) - cnt, cnt], -1).astype(np.int32)
+    ends = (info[:, 0] + info[:, 1] - 1) % 64
+    assert {0, 31, 32, 63} <= set(ends.tolist()) and (cnt == 1).any() and cnt.min() >= 1 and n % 256 != 0
+    return info
+
+
+@functools.lru_cache(maxsize=None)
+def render_case(cut):
+    """renderer, packed batch, upstream gradient and the float64 port's inputs, made once and shared by the backward tests (which
+    set the renderer's switches themselves and leave parameters and batch unchanged)"""
+    renderer, packed, info, bg = _renderer_and_batch()
+    plan = ref.levels(**ref.FINE)
+    assert plan == tuple(renderer.feature_module.plan)
+    if cut:
+        n = packed.size(0) - (1 if (packed.size(0) - 1) % 256 else 2)          # drop a sample or two: not a multiple of 256
+        packed = packed[:n].contiguous()
+        info = torch.from_numpy(_cut_into_rays(n, 11)).to(DEV)
+    R = info.size(0)
+    # U(-1, 1) * 2^10, the trainer's gradient scale: per-level gradients of order 1, well above the rounding of the accumulate case's
+    # one fp32 addition onto a pre-fill of magnitude 2
+    G = (torch.rand((R, 3), generator=torch.Generator().manual_seed(17), dtype=torch.float64) * 2 - 1) * 1024.0
+    sd64 = {k: (v.detach().cpu().double() if v.is_floating_point() else v.detach().cpu()) for k, v in renderer.state_dict().items()}
+    port = dict(sd=sd64, packed=packed.cpu().double(), info=info.cpu(), bg=torch.from_numpy(bg).double(), G=G, plan=plan, memo={})
+    return renderer, packed, info, G.float().to(DEV), port
+
+
+def _split_levels(grads, plan):
+    out = {k: v for k, v in grads.items() if k != "feature_module.table"}
+    for l, (e, o) in enumerate(zip(plan[2], plan[3])):
+        out[f"feature_module.table.level{l:02d}"] = grads["feature_module.table"][o:o + e]
+    return out
+
+
+def _port_grads(port):
+    """d sum(out * G) / d parameter through the float64 port; evaluations the ties helper repeats unchanged (no tie unit forced) are
+    computed once per batch"""
+    from oracle import torch_port as tp
+    ctrl = tp.ReluControl.current            # (the helper installs a fresh one for its base evaluation, forcing ones for flips)
+    forced = ctrl is not None and bool(ctrl.force)
+    key = (tp._Weights.exact_backward, tp._Weights.noise_probe, ctrl is not None)
+    if not forced and key in port["memo"]:
+        grads, found, state = port["memo"][key]
+        if ctrl is not None:
+            ctrl.found.extend(found)
+            ctrl.state.update(state)
+        return grads
+    grads = tp.grads_of(port["sd"], lambda p: (tp.render(p, port["packed"], port["info"], port["bg"], hashgrid=port["plan"]) * port["G"]).sum())[0]
+    grads = _split_levels(grads, port["plan"])
+    if not forced:
+        port["memo"][key] = (grads, list(ctrl.found) if ctrl is not None else [], dict(ctrl.state) if ctrl is not None else {})
+    return grads
+
+
+def _backward_against_the_port(cut, fused_node, accumulate):
+    from _ties import assert_grads_match_up_to_relu_ties
+    renderer, packed, info, G, port = render_case(cut)
+    fm = renderer.feature_module
+    params = dict(renderer.named_parameters())
+    renderer.train()
+    renderer.fused, renderer.accumulate_into_grad = fused_node, accumulate
+    fm.__dict__["accumulate_into_grad"] = accumulate
+    pre, ptrs = {}, {}
+    try:
+        for i, (k, p) in enumerate(params.items()):
+            p.grad = None
+            if accumulate:
+                pre[k] = torch.rand(p.shape, generator=torch.Generator().manual_seed(100 + i)) * 4 - 2
+                p.grad = pre[k].to(DEV)
+                ptrs[k] = p.grad.data_ptr()
+        out = renderer(packed, info)
+        assert out.shape == G.shape and torch.isfinite(out).all()
+        (out * G).sum().backward()
+        got = {}
+        for k, p in params.items():
+            g = p.grad.detach().cpu().double()
+            if accumulate:
+                assert p.grad.data_ptr() == ptrs[k], f"{k}: the gradient tensor was replaced"
+                g = g - pre[k].double()                   # pre-fill + fresh result: what is left must be the fresh result
+            got[k] = g.numpy()
+    finally:
+        renderer.fused, renderer.accumulate_into_grad = True, False
+        fm.__dict__["accumulate_into_grad"] = False
+        for p in params.values():
+            p.grad = None
+    got, want = _split_levels(got, port["plan"]), {}
+    flips = assert_grads_match_up_to_relu_ties(got, lambda: _port_grads(port), 1e-4, weights_conditioning=True, cond_cap=2e-3, matched=want)
+    rel = want.pop("rel")
+    ratios = [float(np.abs(got[k] - want[k]).max() / (rel[k] * np.abs(want[k]).max())) for k in sorted(want) if ".level" in k]
+    print(f"{'fused node' if fused_node else 'module path'}, {'accumulate' if accumulate else 'fresh'}, {packed.size(0)} samples in "
+          f"{info.size(0)} rays: table gradient error / allowance per level, worst {max(ratios):.3f} at level {int(np.argmax(ratios))}; "
+          f"{flips} tie units flipped; smallest per-level max |gradient| {min(float(np.abs(want[k]).max()) for k in want if '.level' in k):.3e}")
+
+
+@pytest.mark.parametrize("accumulate", [False, True], ids=["fresh", "accumulate"])
+@pytest.mark.parametrize("fused_node", [True, False], ids=["fused", "modules"])
+def test_renderer_backward_matches_the_fp64_port(fused_node, accumulate):
+    """Accumulate: the renderer's and the field's switches set as run.Trainer sets them and every .grad pre-filled with U(-2, 2): the
+    result is the pre-fill plus the fresh gradient (the rounding of that one fp32 addition, 2^-24 * 4, is far below 1e-4 of every
+    level's largest element here: the smallest is printed) and every gradient tensor keeps its storage."""
+    _backward_against_the_port(False, fused_node, accumulate)
+
+
+@pytest.mark.parametrize("fused_node", [True, False], ids=["fused", "modules"])
+def test_renderer_backward_on_rays_cut_inside_waves(fused_node):
+    """The same samples cut into other rays: ray ends at lanes 0, 31, 32 and 63 of a wave, rays of one sample, a total that is no
+    multiple of 256 -- what the trainer's ray-ordered batches feed the scan, the composite and the merged scatter on every step."""
+    _backward_against_the_port(True, fused_node, fused_node)
