@@ -21,11 +21,13 @@ and 256.  Which launches that reaches, read off their grid computations (32-samp
   with per_cu = 2 at both widths (launch_wgrad_f2 / launch_wgrad_b3: 48 / 72 KB of LDS, two workgroups per CU), and the width-128 layer
   forward / data-gradient kernels (STREAMS = 2).
 * NOT reached by any n of part A: the cross-layer launches of mlp_fused_f2.hip (the default f16x2 form) run ``min(ceil(n_tiles / NW),
-  256)`` workgroups with NW = 4 or 8 waves, so their second round opens at sample 32768 or 65536; part B's 40037 gives the NW = 4 launches
-  a second round (its probes 40004 and 40036 lie in it), the NW = 8 launches (width-128 chain and inference) run one round at every n here.
-  The width-64 forward / chain launches (8 to 16 tiles per workgroup and round, 256 or 512 workgroups: a second round at sample 65536 or
-  later) run one round as well.
-Part B adds the ragged 40037.
+  256)`` workgroups with NW = 4 or 8 waves, so their second round opens at sample 32768 or 65536.  Part B reaches both: its 40037 gives
+  the NW = 4 launches a second round (its probes 40004 and 40036 lie in it), and cobafa_128x6 also runs at 65573 = 256 x 8 x 32 + 37, where
+  the NW = 8 launches -- the width-128 chain, fused_chain_kernel<128>, and the width-128 inference forward, fused_fwd_kernel<128, false> --
+  open a second round of two tiles, the last one ragged (probes 65535 / 65536 on the round edge, 65540 and 65572 in the second round;
+  the inference forward has a case of its own below, through tn_mlp_fwd_ws).  Still one round at every n here: the width-64 forward /
+  chain launches (8 to 16 tiles per workgroup and round, 256 or 512 workgroups: a second round at sample 65536 or later).
+Part B adds the ragged 40037 and, for cobafa_128x6, the ragged 65573.
 
 The pair backward (tn_mlp_bwd_pair) only takes the 5-layer colour head: four ReLU layers, 98.9 % of the draws hold a tie unit
 (tests/test_mlp_ref.py).  It is therefore held to the bound forward-only (part A, both head outputs, lean and stashed) and its backward
@@ -185,13 +187,16 @@ STACKS_B = {     # name: (spec, tolerance of the stack in test_hip_models.py: pe
     "colour_head":    (R.Spec("dircat", 96, 8, 64, 3, 3, "sigmoid"), 2e-5),
 }
 RAGGED = 40037
+ROUND_NW8 = 256 * 8 * 32                    # samples per round of the cross-layer launches with 8 waves per workgroup (see the docstring)
+RAGGED_NW8 = ROUND_NW8 + 37
 
 
-def _probes(n, width):
+def _probes(n, width, edge=SECOND_ROUND - 1):
     """at most eight probe samples: 0; 31 and 32 (the first tile edge); the last sample before and the first sample of the second
     round (8191 / 8192: the one-tile-per-workgroup launches on 256 workgroups; widths 128 and 256 also 16384: the f16x2 / bf16x3 weight-gradient
-    launches on 512 workgroups and the width-128 layer kernels' two tile streams); n - 33; n - 1"""
-    p = {0, 31, 32, SECOND_ROUND - 2, SECOND_ROUND - 1, n - 33, n - 1}
+    launches on 512 workgroups and the width-128 layer kernels' two tile streams); n - 33; n - 1.  `edge`: the first sample of the second
+    round where it is another launch's (65536: the cross-layer launches with 8 waves; 8191 / 8192 are left to the sizes that have them)"""
+    p = {0, 31, 32, edge - 1, edge, n - 33, n - 1}
     if width >= 128:
         p.add(2 * (SECOND_ROUND - 1))
     p = sorted(q for q in p if 0 <= q < n)
@@ -291,7 +296,7 @@ def _deep(name, n, mode):
     from tinynerf_amd import _lib as L
     spec, rel = STACKS_B[name]
     fx = _fixture("B:" + name, spec, n, reject=False)
-    probes = _probes(n, spec.hidden)
+    probes = _probes(n, spec.hidden, ROUND_NW8 if n > ROUND_NW8 else SECOND_ROUND - 1)
     pt = torch.tensor(probes, device=DEV)
     others = torch.ones(n, dtype=torch.bool, device=DEV)
     others[pt] = False
@@ -321,7 +326,7 @@ def _deep(name, n, mode):
             print(f"{what}: {len(probes)} probes, tie units flipped: sparse {flips}, dense {flips2}")
 
 
-_WIDE_B = [(k, n) for k in ("vanilla_256x10", "cobafa_128x6") for n in _sizes(STACKS_B[k][0], (RAGGED,))]
+_WIDE_B = [(k, n) for k in ("vanilla_256x10", "cobafa_128x6") for n in _sizes(STACKS_B[k][0], (RAGGED,))] + [("cobafa_128x6", RAGGED_NW8)]
 _HEADS_B = [(k, n) for k in ("sigma_head", "colour_head") for n in _sizes(STACKS_B[k][0], (RAGGED,))]
 
 
@@ -333,6 +338,42 @@ def test_deep_wide_stack_sparse_upstream(name, n, matmul):
 @pytest.mark.parametrize("name,n", _HEADS_B)
 def test_deep_head_sparse_upstream(name, n, heads):
     _deep(name, n, heads)
+
+
+def test_cobafa_inference_second_round_of_the_eight_wave_launch(monkeypatch):
+    """The inference forward of cobafa_128x6 in f16x2 mode at 65573 samples: fused_fwd_kernel<128, false> (8 waves per workgroup, 256
+    workgroups) opens its second round at sample 65536, with two tiles, the last one ragged.  Through tn_mlp_fwd_ws -- the entry that runs
+    the cross-layer launch, as models._FusedMLP calls it -- and through tn_mlp_fwd (the register-resident kernel of mlp.hip), each into a
+    NaN-prefilled y: every element finite, and y within the stack's 3e-5 of its largest element of oracle/torch_port.mlp on the device."""
+    from oracle import torch_port as tp
+    from tinynerf_amd import _lib as L, models as m
+    monkeypatch.setattr(m, "MATMUL", "f16x2")
+    name, n = "cobafa_128x6", RAGGED_NW8
+    spec, rel = STACKS_B[name]
+    fx = _fixture("B:" + name, spec, n, reject=False)
+    params = [cu(t) for wb in fx.layers for t in wb]
+    x = cu(fx.x)
+    with torch.no_grad():
+        ref = tp.mlp({f"net.{i}.{k}": t for i in range(len(fx.layers)) for k, t in (("weight", params[2 * i]), ("bias", params[2 * i + 1]))},
+                     "net.", x)
+    top = float(ref.abs().max())
+    d = m._mlp_desc(params, x.size(1), L.ENC_NONE, 0, L.ACT_NONE, None)
+    assert d.flags & L.MLP_F16X2
+    fn = L.lib().tn_mlp_fwd_workspace_bytes
+    fn.restype = C.c_int64
+    nb = int(fn(C.byref(d), C.c_int64(n)))
+    assert nb > 0, "no workspace form: tn_mlp_fwd_ws would not run the cross-layer launch"
+    ws = torch.full((nb // 4,), float("nan"), device=DEV)
+    for entry in ("tn_mlp_fwd_ws", "tn_mlp_fwd"):
+        y = torch.full((n, spec.out), float("nan"), device=DEV)
+        if entry == "tn_mlp_fwd_ws":
+            L.call(entry, x.device, C.byref(d), L.ptr(x), C.c_void_p(None), C.c_int64(n), L.ptr(y), L.ptr(ws), C.c_int64(nb))
+        else:
+            L.call(entry, x.device, C.byref(d), L.ptr(x), C.c_void_p(None), C.c_int64(n), L.ptr(y), C.c_void_p(None))
+        assert bool(torch.isfinite(y).all()), f"{entry}: {int((~torch.isfinite(y)).any(1).sum())} samples of y are not finite"
+        err = float((y - ref).abs().max())
+        print(f"{entry} {name} n={n} f16x2: max |y - port| = {err:.3e} = {err / top:.3e} of the largest element {top:.4f}")
+        assert err <= rel * top, f"{entry}: {err / top:.3e} of the largest element, allowed {rel:.0e}"
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -51,8 +51,7 @@ __global__ __launch_bounds__(TN_DX_WAVES * 64) void heads_dx_f2_kernel(DxArgs a,
     auto wv = [&](int nn, int col) { return nn < 64 ? a.w_a[(int64_t)nn * a.ld_a + a.col0_a + col] : a.w_b[(int64_t)(nn - 64) * a.ld_b + a.col0_b + col]; };
     float m = 0.0f;
     for (int e = threadIdx.x; e < 128 * F; e += NW * 64) m = fmaxf(m, fabsf(wv(e / F, e % F)));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = tn::wave_max(m);
     if (lane == 0) scratch[wave] = m;
     __syncthreads();
     float g = 0.0f;

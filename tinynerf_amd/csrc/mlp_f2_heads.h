@@ -93,8 +93,7 @@ __device__ inline void stage_weights_f2(const MlpArgs &a, float *lds) {
         const int K = a.K[l], N = a.N[l], Kp = a.stride[l] - 8;
         float m = 0.0f;
         for (int e = threadIdx.x; e < N * K; e += blockDim.x) m = fmaxf(m, fabsf(a.W[l][e]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        m = tn::wave_max(m);
         __syncthreads();                                    // (scratch of the previous layer has been read)
         if (lane == 0) scratch[wave] = m;
         __syncthreads();

@@ -282,15 +282,13 @@ struct Stream2 : TileWalk<F2Geom<H>::STREAMS, F2Geom<H>::WPS> {
     __device__ __forceinline__ void report_max(float *dst) const {
         if (dst == nullptr) return;
         float m = seen;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        m = tn::wave_max(m);
         if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(dst), __float_as_uint(m));
     }
     // the layer's weight scale from every wave's largest |weight| (prologue)
     __device__ __forceinline__ void layer_scale(float wmax, float &s, float &inv) const {
         float m = wmax;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+        m = tn::wave_max(m);
         if (lane == 0) red[wave] = m;
         __syncthreads();
         float g = 0.0f;
@@ -604,8 +602,7 @@ __global__ __launch_bounds__(WPB * 64) void fwd_first_f2_kernel(FwdLayerArgs a, 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     float m = 0.0f;
     for (int e = threadIdx.x; e < a.N * a.K; e += blockDim.x) m = fmaxf(m, fabsf(a.W[e]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    m = tn::wave_max(m);
     if (lane == 0) red[wave] = m;
     for (int e = threadIdx.x; e < H; e += blockDim.x) bias_s[e] = e < a.N ? a.B[e] : 0.0f;
     __syncthreads();

@@ -79,6 +79,17 @@ constexpr int NRING = 4;
 template <int H, bool CHAIN_OR_INFER> constexpr int NWAVES = (H == 128 && CHAIN_OR_INFER) ? 8 : 4;
 constexpr int KS0 = 4;                       // k steps of the first layer (<= 64 input rows)
 
+// The dynamic LDS block of a persistent launch over L layers, in bytes: the ring, the bias table [L][H] (BIAS: the forward), the maxima table
+// [L][64 NW] -- one float per lane and layer -- (MAXIMA: training forward and chain), 64 B.  The kernels, run_layer and the launches take
+// every offset from here.
+template <int H, int NW, bool BIAS, bool MAXIMA>
+struct FusedLds {
+    static constexpr __host__ __device__ unsigned bias_off() { return NRING * CHUNK_B; }
+    static constexpr __host__ __device__ unsigned maxima_off(int L) { return bias_off() + (BIAS ? (unsigned)(L * H) * 4u : 0u); }
+    static constexpr __host__ __device__ unsigned maxima_stride() { return 256u * NW; }
+    static constexpr __host__ __device__ size_t bytes(int L) { return (size_t)maxima_off(L) + (MAXIMA ? (size_t)L * maxima_stride() : 0) + 64; }
+};
+
 struct FusedArgs {
     const unsigned char *stream;     // packed weights of all layers, consumption order (tn_fused_pack)
     const float *bias;               // [L][H], zero padded
@@ -140,9 +151,7 @@ __global__ __launch_bounds__(1024) void fused_pack_kernel(PackArgs a)
         for (int r = wave; r < N; r += n_waves) {
             float s2 = 0.0f;
             for (int k = lane; k < K; k += 64) { const float w = fabsf(W[(int64_t)r * ldw + k]); wmax = fmaxf(wmax, w); s2 += w; }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
-            n2 = fmaxf(n2, s2);
+            n2 = fmaxf(n2, tn::wave_sum(s2));
         }
         for (int r = threadIdx.x; r < N; r += blockDim.x) bmax = fmaxf(bmax, fabsf(a.B[l][r]));
     } else {
@@ -155,7 +164,7 @@ __global__ __launch_bounds__(1024) void fused_pack_kernel(PackArgs a)
         if (part == 0 && rb < N) { float t = 0.0f; for (int q = 0; q < parts; ++q) t += colsum[q][rb]; n2 = t; }
     }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
+    for (int o = 32; o > 0; o >>= 1) {          // (three butterflies step by step: as three tn::wave_max the waits on the shuffles move, LABNOTES 9.14)
         wmax = fmaxf(wmax, __shfl_xor(wmax, o, 64)); n2 = fmaxf(n2, __shfl_xor(n2, o, 64)); bmax = fmaxf(bmax, __shfl_xor(bmax, o, 64));
     }
     if (lane == 0) { red[0][wave] = wmax; red[1][wave] = n2; red[2][wave] = bmax; }
@@ -236,10 +245,30 @@ struct Ring {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void *)(lds_wave + iss_slot * CHUNK_B + E * 1024), 16,
                                                  (int)voff, (int)(iss_off + E * 1024), 0, 0);
     }
+    template <int... E> __device__ __forceinline__ void pieces(std::integer_sequence<int, E...>) { (piece<E>(), ...); }
     __device__ __forceinline__ void target_next() {                // the chunk the next 8 pieces belong to: g + 3
         iss_slot = (g + 3) & (NRING - 1);
         iss_off = next * CHUNK_B;
         next = next + 1 == n_chunks ? 0 : next + 1;
+    }
+    // The stream start of a workgroup of NW waves whose dynamic LDS begins with the ring at `lds3`: chunks 0, 1, 2 of the stream into slots
+    // 0, 1, 2, the wave's 32 / NW pieces of each.  Ring state = "no boundary passed": the first boundary (step 0 of round 0) makes chunk 0
+    // (slot 0) current, chunk 1 next, and targets the pieces of chunk 3
+    template <int NW> __device__ __forceinline__ void start(const FusedArgs &a, lds_u8 *lds3, int wave, int lane) {
+        rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.stream, 0, 0x7fffffff, 0x00020000);
+        lds_wave = lds3 + wave * (CHUNK_B / NW);
+        voff = (unsigned)(wave * (CHUNK_B / NW) + lane * 16);
+        rd0 = (unsigned)(uintptr_t)lds3 + lane * 16;
+        n_chunks = (unsigned)a.n_chunks;
+        next = 0;
+        g = (unsigned)-3;
+        for (int k = 0; k < 3; ++k) {
+            target_next();
+            pieces(std::make_integer_sequence<int, 32 / NW>{});
+            ++g;
+        }
+        cur = nxt = rd0;
+        __syncthreads();                         // (vmcnt(0): all three chunks have landed; whatever the kernel staged in front of the call as well)
     }
     // between the last MFMA on chunk g - 1 and the first on chunk g
     template <int NW> __device__ __forceinline__ void boundary() {   // (vmcnt: the wave's pieces of one chunk -- the newest -- may still be in flight)
@@ -266,6 +295,13 @@ template <int H> struct State {
     Op2 aw[4][2];                    // operand window: k steps t, t + 1, t + 2 (slot t & 3), two blocks each
     Pending pend;
     float xmax;                      // largest scaled output of the layer being finished (this lane's half of the features)
+
+    __device__ __forceinline__ void prime(unsigned base) {     // operands of stream steps 0 and 1 -- chunk 0, at `base` -- for the window
+        aw[0][0].hi = lds16<0>(base); aw[0][0].lo = lds16<1024>(base);
+        aw[0][1].hi = lds16<PAIR_B>(base); aw[0][1].lo = lds16<PAIR_B + 1024>(base);
+        aw[1][0].hi = lds16<2 * PAIR_B>(base); aw[1][0].lo = lds16<2 * PAIR_B + 1024>(base);
+        aw[1][1].hi = lds16<3 * PAIR_B>(base); aw[1][1].lo = lds16<3 * PAIR_B + 1024>(base);
+    }
 };
 
 // value pair (D registers r0, r0 + 1) of a finished hidden block -> one packed register of the next layer's hi plane and lo plane, in five
@@ -398,13 +434,12 @@ struct Layer {
             if constexpr (PH == 4 && (Q & 7) == 7) bits_[(2 * (2 * grp + blk)) * 32 + lane] = bitacc[blk];
         }
     }
-    template <int Q> __device__ __forceinline__ void flush_pending() {     // a pending pair with nothing to hide behind (end of a TN_MLP_SKIP_LAST stack)
-        hidden_phase<Q, 0>(st.pend.c, st.pend.bias, st.pend.cmul, st.pend.s_out, in, NG - 1, st.pend.rows, st.pend.bits);
-        hidden_phase<Q, 1>(st.pend.c, st.pend.bias, st.pend.cmul, st.pend.s_out, in, NG - 1, st.pend.rows, st.pend.bits);
-        hidden_phase<Q, 2>(st.pend.c, st.pend.bias, st.pend.cmul, st.pend.s_out, in, NG - 1, st.pend.rows, st.pend.bits);
-        hidden_phase<Q, 3>(st.pend.c, st.pend.bias, st.pend.cmul, st.pend.s_out, in, NG - 1, st.pend.rows, st.pend.bits);
-        hidden_phase<Q, 4>(st.pend.c, st.pend.bias, st.pend.cmul, st.pend.s_out, in, NG - 1, st.pend.rows, st.pend.bits);
+    // the pending pairs with nothing to hide behind (end of a TN_MLP_SKIP_LAST stack, end of the chain): pair by pair, phase by phase
+    template <int Q, int... PH> __device__ __forceinline__ void flush_pair(std::integer_sequence<int, PH...>) {
+        (hidden_phase<Q, PH>(st.pend.c, st.pend.bias, st.pend.cmul, st.pend.s_out, in, NG - 1, st.pend.rows, st.pend.bits), ...);
     }
+    template <int... Q> __device__ __forceinline__ void flush_pending(std::integer_sequence<int, Q...>) { (flush_pair<Q>(std::make_integer_sequence<int, 5>{}), ...); }
+    __device__ __forceinline__ void flush_pending() { flush_pending(std::make_integer_sequence<int, 16>{}); }
     // NPAIR pairs Q0 .. Q0 + NPAIR - 1 dealt over the six gaps of a step
     template <int Q0, int NPAIR>
     __device__ __forceinline__ void hidden_gap(int gap, const f32x16 (&cc)[2], const f32x4 (&bb)[2][4], float cm, float so, Op2 (&dst)[KS], int grp,
@@ -443,6 +478,12 @@ struct Layer {
 #pragma unroll
             for (int u = 0; u < 4; ++u) if (own_tile) *reinterpret_cast<float *>(p + off + (u + 8 * q) * 128) = store ? v[u] : 0.0f;
         }
+    }
+    // the output layer's last two blocks have nothing to hide behind
+    template <int... Q4> __device__ __forceinline__ void flush_out(std::integer_sequence<int, Q4...>) { (out_quad<Q4>(st.pend.c, st.pend.bias, NG - 1), ...); }
+    __device__ __forceinline__ void flush_out() {
+        wait_bias<0>(st.pend.bias);
+        flush_out(std::make_integer_sequence<int, 8>{});
     }
     template <int BLK> __device__ __forceinline__ void load_mask(f32x4 (&bb)[2][4], int grp) {       // MODE 2: relu' bits of the block the gradient flows into
         bb[BLK][0][0] = __uint_as_float(bits[(2 * (2 * grp + BLK)) * 32 + lane]);
@@ -545,12 +586,62 @@ struct Tile {
     float *yrow; bool store, own_tile; int h, lane;
     unsigned lane_off;
     float *rows_base;              // STASH: workspace + tile * rows_total * 32 floats (wave-uniform)
-    unsigned max0;                 // STASH: LDS address of this lane's slot in the maxima table of layer 0 (layer l: + l * 1024)
+    unsigned max0;                 // STASH: LDS address of this lane's slot in the maxima table of layer 0 (layer l: + l * FusedLds::maxima_stride())
 };
 
+// The tiles of a persistent launch: gridDim.x NW per round, wave by wave; a wave without a tile of its own in the last round takes the
+// last tile (it recomputes it and writes the same values to the same places)
+template <int NW> struct Rounds {
+    int64_t n_tiles, rounds;
+    __device__ __forceinline__ explicit Rounds(int64_t n) : n_tiles((n + 31) >> 5) {
+        const int64_t per_round = (int64_t)gridDim.x * NW;
+        rounds = (n_tiles + per_round - 1) / per_round;
+    }
+    __device__ __forceinline__ int64_t tile(int64_t round, int wave, bool &tile_ok) const {
+        const int64_t tile_raw = (round * gridDim.x + blockIdx.x) * NW + wave;
+        tile_ok = tile_raw < n_tiles;
+        return tile_ok ? tile_raw : n_tiles - 1;
+    }
+};
+
+// A sample column out of 32 NT rows of the tile at `in`, read in the D layout (mlp_f2_layers.hip fwd_first_f2_kernel): the exact column
+// maximum, its scale, the column as operands in st.Q[0 .. 2 NT - 1]; -> 1 / scale
+template <int NT, int H>
+__device__ __forceinline__ float load_column(const float *in, State<H> &st, int j, int h)
+{
+    float x[NT][16];
+    float mx = 0.0f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { x[t][r] = in[(32 * t + frow(r, h)) * 32 + j]; mx = fmaxf(mx, fabsf(x[t][r])); }
+    mx = f2_xmax(mx);
+    float s_in, inv_in;
+    f2_scales(mx, s_in, inv_in);
+    st.xmax = mx * s_in;
+#pragma unroll
+    for (int b = 0; b < 2 * NT; ++b) {
+        float v[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = x[b >> 1][8 * (b & 1) + e] * s_in;
+        f2_split8(v, 1.0f, st.Q[b].hi, st.Q[b].lo);
+    }
+    return inv_in;
+}
+
+// A Layer that runs no step of its own: what flush_pending reads of one (the pending blocks carry their factors and destinations)
+template <int H, int MODE, bool STASH>
+__device__ __forceinline__ Layer<H, H / 16, MODE, true, STASH> flush_layer(Ring &ring, State<H> &st, float inv_in, const Tile &tl)
+{
+    Layer<H, H / 16, MODE, true, STASH> L{ring, st, st.P, st.Q, 0u, 0.0f, 0.0f, 0.0f, inv_in, 0.0f, 0.0f, 0.0f, tl.yrow, tl.store, tl.h};
+    L.lane_off = tl.lane_off; L.lane = tl.lane; L.max_addr = 0; L.own_tile = tl.own_tile;
+    return L;
+}
+
+// layer l of the launch on the wave's tile, ready to run
 template <int H, int KSL, int MODE, bool HAS_PREV, bool STASH>
-__device__ __forceinline__ float run_layer(Ring &ring, State<H> &st, Op2 (&in)[H / 16], Op2 (&out)[H / 16], const FusedArgs &a, int l, unsigned bias0,
-                                           float inv_in, const Tile &tl)
+__device__ __forceinline__ Layer<H, KSL, MODE, HAS_PREV, STASH> make_layer(Ring &ring, State<H> &st, Op2 (&in)[H / 16], Op2 (&out)[H / 16], const FusedArgs &a, int l,
+                                                                            unsigned bias0, float inv_in, const Tile &tl)
 {
     const float *cs = a.consts + 4 * l;
     Layer<H, KSL, MODE, HAS_PREV, STASH> L{ring, st, in, out, bias0 + (unsigned)(l * H * 4), cs[0], cs[1], cs[2], inv_in, 0.0f, 0.0f, 0.0f, tl.yrow, tl.store, tl.h};
@@ -558,152 +649,114 @@ __device__ __forceinline__ float run_layer(Ring &ring, State<H> &st, Op2 (&in)[H
         L.rows = urow(tl.rows_base, a.off_out[l]);
         L.bits = reinterpret_cast<unsigned *>(urow(tl.rows_base, MODE != 1 ? a.off_bits[l] : 0));
         L.lane_off = tl.lane_off; L.lane = tl.lane;
-        L.max_addr = (a.tail != nullptr && a.tail_idx[l] >= 0) ? tl.max0 + (unsigned)l * (256u * NWAVES<H, MODE == 2 || !STASH>) : 0u;
+        constexpr unsigned stride = FusedLds<H, NWAVES<H, MODE == 2 || !STASH>, MODE != 2, true>::maxima_stride();
+        L.max_addr = (a.tail != nullptr && a.tail_idx[l] >= 0) ? tl.max0 + (unsigned)l * stride : 0u;
     }
     L.own_tile = tl.own_tile;
+    return L;
+}
+
+template <int H, int KSL, int MODE, bool HAS_PREV, bool STASH>
+__device__ __forceinline__ float run_layer(Ring &ring, State<H> &st, Op2 (&in)[H / 16], Op2 (&out)[H / 16], const FusedArgs &a, int l, unsigned bias0,
+                                           float inv_in, const Tile &tl)
+{
+    auto L = make_layer<H, KSL, MODE, HAS_PREV, STASH>(ring, st, in, out, a, l, bias0, inv_in, tl);
     L.run();
     return L.inv_out;
+}
+
+// Layers l .. last of the launch, all H -> H with the layer below them still pending, from st.P: in pairs P -> Q -> P.  An odd number of
+// them (Cobafa: 5): a third copy of the loop body would cost 12 KB of code; instead the last one runs P -> Q like the others and the
+// column moves back once per round (H / 2 register moves).  The column ends in st.P either way and l at last + 1: the forward's output
+// layer takes its index from there (with last + 1 spelt at that call, fused_fwd_kernel<128, true> selects two v_fma_f32 where it has
+// one v_pk_fma_f32, LABNOTES 9.14).
+template <int H, int MODE, bool STASH>
+__device__ __forceinline__ float hidden_walk(Ring &ring, State<H> &st, const FusedArgs &a, int &l, int last, unsigned bias0, float inv_in, const Tile &tl)
+{
+    constexpr int KS = H / 16;
+#pragma clang loop unroll(disable)
+    for (; l + 1 <= last; l += 2) {
+        inv_in = run_layer<H, KS, MODE, true, STASH>(ring, st, st.P, st.Q, a, l, bias0, inv_in, tl);
+        inv_in = run_layer<H, KS, MODE, true, STASH>(ring, st, st.Q, st.P, a, l + 1, bias0, inv_in, tl);
+    }
+    if (l <= last) {
+        inv_in = run_layer<H, KS, MODE, true, STASH>(ring, st, st.P, st.Q, a, l, bias0, inv_in, tl);
+#pragma unroll
+        for (int b = 0; b < KS - 4; ++b) st.P[b] = st.Q[b];          // (the last four operand steps are still pending: st.pend writes them into P)
+        ++l;
+    }
+    return inv_in;
+}
+
+// End of a kernel: the lanes' running maxima of every layer that wants one -> tail (the ring's last requests have landed: nothing may
+// arrive in LDS after the workgroup has gone)
+template <class Lds>
+__device__ __forceinline__ void publish_maxima(const FusedArgs &a, const unsigned char *lds_raw, int lane)
+{
+    if (a.tail == nullptr) return;
+    const float *max_s = reinterpret_cast<const float *>(lds_raw + Lds::maxima_off(a.L));
+    __syncthreads();
+    for (int l = 0; l < a.L; ++l) {
+        if (a.tail_idx[l] < 0) continue;
+        const float m = tn::wave_max(max_s[l * (Lds::maxima_stride() / 4) + threadIdx.x]);
+        if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(a.tail + a.tail_idx[l]), __float_as_uint(m));      // (non-negative floats order like their bits)
+    }
 }
 
 template <int H, bool STASH>
 __global__ __launch_bounds__((64 * NWAVES<H, !STASH>)) void fused_fwd_kernel(FusedArgs a, int64_t n)
 {
-    constexpr int KS = H / 16, NB = H / 32;
+    constexpr int KS = H / 16, NW = NWAVES<H, !STASH>;
+    using Lds = FusedLds<H, NW, true, STASH>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    float *bias_s = reinterpret_cast<float *>(lds_raw + NRING * CHUNK_B);
-    float *max_s = bias_s + a.L * H;                           // STASH: [L][256] running maxima of the layers' inputs
+    float *bias_s = reinterpret_cast<float *>(lds_raw + Lds::bias_off());
+    float *max_s = reinterpret_cast<float *>(lds_raw + Lds::maxima_off(a.L));     // STASH: [L][64 NW] running maxima of the layers' inputs
     const int lane = tn::lane_id(), j = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     for (int e = threadIdx.x; e < a.L * H; e += blockDim.x) bias_s[e] = a.bias[e];
-    if constexpr (STASH) for (int e = threadIdx.x; e < a.L * 64 * NWAVES<H, !STASH>; e += blockDim.x) max_s[e] = 0.0f;
+    if constexpr (STASH) for (int e = threadIdx.x; e < a.L * (int)(Lds::maxima_stride() / 4); e += blockDim.x) max_s[e] = 0.0f;
     lds_u8 *lds3 = (lds_u8 *)lds_raw;
     const unsigned lds0 = (unsigned)(uintptr_t)lds3;
     Ring ring;
-    ring.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.stream, 0, 0x7fffffff, 0x00020000);
-    constexpr int NW = NWAVES<H, !STASH>;
-    ring.lds_wave = lds3 + wave * (CHUNK_B / NW);
-    ring.voff = (unsigned)(wave * (CHUNK_B / NW) + lane * 16);
-    ring.rd0 = lds0 + lane * 16;
-    ring.n_chunks = (unsigned)a.n_chunks;
-    ring.next = 0;
-    // chunks 0, 1, 2 of the stream into slots 0, 1, 2.  Ring state = "no boundary passed": the first boundary (step 0 of round 0) makes
-    // chunk 0 (slot 0) current, chunk 1 next, and targets the pieces of chunk 3
-    ring.g = (unsigned)-3;
-    for (int k = 0; k < 3; ++k) {
-        ring.target_next();
-        ring.template piece<0>(); ring.template piece<1>(); ring.template piece<2>(); ring.template piece<3>();
-        if constexpr (NW == 4) { ring.template piece<4>(); ring.template piece<5>(); ring.template piece<6>(); ring.template piece<7>(); }
-        ++ring.g;
-    }
-    ring.cur = ring.nxt = ring.rd0;
-    __syncthreads();                         // (vmcnt(0): all three chunks have landed; bias staged)
-    const unsigned bias0 = lds0 + NRING * CHUNK_B + 16 * h;
-    const int64_t n_tiles = (n + 31) >> 5;
-    const int64_t per_round = (int64_t)gridDim.x * NW;
-    const int64_t rounds = (n_tiles + per_round - 1) / per_round;
+    ring.template start<NW>(a, lds3, wave, lane);              // (behind its barrier the bias is staged as well)
+    const unsigned bias0 = lds0 + Lds::bias_off() + 16 * h;
+    const Rounds<NW> rounds(n);
     State<H> st;
-    // (operands of stream steps 0 and 1 -- chunk 0 -- for the window)
-    {
-        const unsigned base = ring.rd0;
-        st.aw[0][0].hi = lds16<0>(base); st.aw[0][0].lo = lds16<1024>(base);
-        st.aw[0][1].hi = lds16<PAIR_B>(base); st.aw[0][1].lo = lds16<PAIR_B + 1024>(base);
-        st.aw[1][0].hi = lds16<2 * PAIR_B>(base); st.aw[1][0].lo = lds16<2 * PAIR_B + 1024>(base);
-        st.aw[1][1].hi = lds16<3 * PAIR_B>(base); st.aw[1][1].lo = lds16<3 * PAIR_B + 1024>(base);
-    }
+    st.prime(ring.rd0);
     Tile tl;
     tl.h = h; tl.lane = lane;
     tl.lane_off = (unsigned)(4 * h * 32 + j) * 4u;
     asm volatile("" : "+v"(tl.lane_off));
-    tl.max0 = lds0 + NRING * CHUNK_B + (unsigned)(a.L * H) * 4u + (unsigned)threadIdx.x * 4u;
+    tl.max0 = lds0 + Lds::maxima_off(a.L) + (unsigned)threadIdx.x * 4u;
     const int n_hidden = a.L - 1 - (a.out_linear ? 1 : 0);     // hidden layers behind layer 0
 #pragma clang loop unroll(disable)
-    for (int64_t round = 0; round < rounds; ++round) {
-        const int64_t tile_raw = (round * gridDim.x + blockIdx.x) * NW + wave;
-        const bool tile_ok = tile_raw < n_tiles;
-        const int64_t tile = tile_ok ? tile_raw : n_tiles - 1;
-        float inv_in;
-        {   // first-layer inputs: 64 rows of the tile in the D layout (mlp_f2_layers.hip fwd_first_f2_kernel), exact column maximum
-            const float *in = urow(a.e_rows, tile * a.e_rows_total + a.e_off);
-            float x[2][16];
-            float mx = 0.0f;
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { x[t][r] = in[(32 * t + frow(r, h)) * 32 + j]; mx = fmaxf(mx, fabsf(x[t][r])); }
-            mx = f2_xmax(mx);
-            float s_in;
-            f2_scales(mx, s_in, inv_in);
-            st.xmax = mx * s_in;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = x[b >> 1][8 * (b & 1) + e] * s_in;
-                f2_split8(v, 1.0f, st.Q[b].hi, st.Q[b].lo);
-            }
-        }
+    for (int64_t round = 0; round < rounds.rounds; ++round) {
+        const int64_t tile = rounds.tile(round, wave, tl.own_tile);
+        // first-layer inputs: 64 rows of the tile
+        float inv_in = load_column<2>(urow(a.e_rows, tile * a.e_rows_total + a.e_off), st, j, h);
         tl.yrow = a.y != nullptr ? a.y + (tile * 32 + j) * H : nullptr;
-        tl.store = tile_ok && tile * 32 + j < n;
-        tl.own_tile = tile_ok;
-        // (a wave without a tile of its own recomputes the last tile and writes the same values to the same places)
+        tl.store = tl.own_tile && tile * 32 + j < n;
         if constexpr (STASH) tl.rows_base = urow(a.rows, tile * a.rows_total);
-        // layer 0: Q (4 operand steps) -> P; hidden layers in pairs P -> Q -> P; output layer (or the flush of the last hidden layer) from P
+        // layer 0: Q (4 operand steps) -> P; hidden layers from P back into P; output layer (or the flush of the last hidden layer) from P
         inv_in = run_layer<H, KS0, 0, false, STASH>(ring, st, st.Q, st.P, a, 0, bias0, inv_in, tl);
         int l = 1;
-#pragma clang loop unroll(disable)
-        for (; l + 1 <= n_hidden; l += 2) {
-            inv_in = run_layer<H, KS, 0, true, STASH>(ring, st, st.P, st.Q, a, l, bias0, inv_in, tl);
-            inv_in = run_layer<H, KS, 0, true, STASH>(ring, st, st.Q, st.P, a, l + 1, bias0, inv_in, tl);
-        }
-        if (l <= n_hidden) {                 // an odd number of hidden layers (Cobafa: 5): a third copy of the loop body would cost 12 KB of code;
-            // instead the last one runs P -> Q like the others and the column moves back once per round (H / 2 register moves)
-            inv_in = run_layer<H, KS, 0, true, STASH>(ring, st, st.P, st.Q, a, l, bias0, inv_in, tl);
-#pragma unroll
-            for (int b = 0; b < KS - 4; ++b) st.P[b] = st.Q[b];          // (the last four operand steps are still pending: st.pend writes them into P)
-            ++l;
-        }
+        inv_in = hidden_walk<H, 0, STASH>(ring, st, a, l, n_hidden, bias0, inv_in, tl);
         if (a.out_linear) {
-            const float *cs = a.consts + 4 * l;
-            Layer<H, KS, 1, true, STASH> L{ring, st, st.P, st.Q, bias0 + (unsigned)(l * H * 4), cs[0], cs[1], cs[2], inv_in, 0.0f, 0.0f, 0.0f, tl.yrow, tl.store, h};
-            if constexpr (STASH) {
-                L.rows = urow(tl.rows_base, a.off_out[l]); L.bits = nullptr; L.lane_off = tl.lane_off; L.lane = lane;
-                L.max_addr = (a.tail != nullptr && a.tail_idx[l] >= 0) ? tl.max0 + (unsigned)l * (256u * NWAVES<H, !STASH>) : 0u;
-            }
-            L.own_tile = tile_ok;
+            auto L = make_layer<H, KS, 1, true, STASH>(ring, st, st.P, st.Q, a, l, bias0, inv_in, tl);
             L.run();
-            // its last two blocks have nothing to hide behind
-            wait_bias<0>(st.pend.bias);
-            L.template out_quad<0>(st.pend.c, st.pend.bias, NB / 2 - 1); L.template out_quad<1>(st.pend.c, st.pend.bias, NB / 2 - 1);
-            L.template out_quad<2>(st.pend.c, st.pend.bias, NB / 2 - 1); L.template out_quad<3>(st.pend.c, st.pend.bias, NB / 2 - 1);
-            L.template out_quad<4>(st.pend.c, st.pend.bias, NB / 2 - 1); L.template out_quad<5>(st.pend.c, st.pend.bias, NB / 2 - 1);
-            L.template out_quad<6>(st.pend.c, st.pend.bias, NB / 2 - 1); L.template out_quad<7>(st.pend.c, st.pend.bias, NB / 2 - 1);
+            L.flush_out();
         } else {
             // TN_MLP_SKIP_LAST: the stack ends in a hidden activation -- its last two blocks are finished here (rows and bit rows; the
             // operands they would become have no consumer)
             if constexpr (STASH) {
-                Layer<H, KS, 0, true, STASH> L{ring, st, st.P, st.Q, bias0, 0.0f, 0.0f, 0.0f, inv_in, 0.0f, 0.0f, 0.0f, tl.yrow, tl.store, h};
-                L.lane_off = tl.lane_off; L.lane = lane; L.max_addr = 0; L.own_tile = tile_ok;
+                auto L = flush_layer<H, 0, STASH>(ring, st, inv_in, tl);
                 wait_bias<0>(st.pend.bias);
-                L.template flush_pending<0>(); L.template flush_pending<1>(); L.template flush_pending<2>(); L.template flush_pending<3>();
-                L.template flush_pending<4>(); L.template flush_pending<5>(); L.template flush_pending<6>(); L.template flush_pending<7>();
-                L.template flush_pending<8>(); L.template flush_pending<9>(); L.template flush_pending<10>(); L.template flush_pending<11>();
-                L.template flush_pending<12>(); L.template flush_pending<13>(); L.template flush_pending<14>(); L.template flush_pending<15>();
+                L.flush_pending();
             }
         }
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");      // (the ring's last requests: nothing may land in LDS after the workgroup has gone)
-    if constexpr (STASH) {
-        if (a.tail != nullptr) {
-            __syncthreads();
-            for (int l = 0; l < a.L; ++l) {
-                if (a.tail_idx[l] < 0) continue;
-                float m = max_s[l * 64 * NW + threadIdx.x];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-                if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(a.tail + a.tail_idx[l]), __float_as_uint(m));      // (non-negative floats order like their bits)
-            }
-        }
-    }
+    if constexpr (STASH) publish_maxima<Lds>(a, lds_raw, lane);
 }
 
 // The data-gradient chain of a wide stack in the same form (round 6): from the gradient w.r.t. the top layer's pre-activation (rows at
@@ -713,141 +766,116 @@ __global__ __launch_bounds__((64 * NWAVES<H, !STASH>)) void fused_fwd_kernel(Fus
 template <int H>
 __global__ __launch_bounds__((64 * NWAVES<H, true>)) void fused_chain_kernel(FusedArgs a, int64_t n)
 {
-    constexpr int KS = H / 16, NB = H / 32;
+    constexpr int KS = H / 16, NB = H / 32, NW = NWAVES<H, true>;
+    using Lds = FusedLds<H, NW, false, true>;
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-    float *max_s = reinterpret_cast<float *>(lds_raw + NRING * CHUNK_B);           // [L][256] running maxima of the layers' input gradients
+    float *max_s = reinterpret_cast<float *>(lds_raw + Lds::maxima_off(a.L));      // [L][64 NW] running maxima of the layers' input gradients
     const int lane = tn::lane_id(), j = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    for (int e = threadIdx.x; e < a.L * 64 * NWAVES<H, true>; e += blockDim.x) max_s[e] = 0.0f;
+    for (int e = threadIdx.x; e < a.L * (int)(Lds::maxima_stride() / 4); e += blockDim.x) max_s[e] = 0.0f;
     lds_u8 *lds3 = (lds_u8 *)lds_raw;
     const unsigned lds0 = (unsigned)(uintptr_t)lds3;
     Ring ring;
-    ring.rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)a.stream, 0, 0x7fffffff, 0x00020000);
-    constexpr int NW = NWAVES<H, true>;
-    ring.lds_wave = lds3 + wave * (CHUNK_B / NW);
-    ring.voff = (unsigned)(wave * (CHUNK_B / NW) + lane * 16);
-    ring.rd0 = lds0 + lane * 16;
-    ring.n_chunks = (unsigned)a.n_chunks;
-    ring.next = 0;
-    ring.g = (unsigned)-3;
-    for (int k = 0; k < 3; ++k) {
-        ring.target_next();
-        ring.template piece<0>(); ring.template piece<1>(); ring.template piece<2>(); ring.template piece<3>();
-        if constexpr (NW == 4) { ring.template piece<4>(); ring.template piece<5>(); ring.template piece<6>(); ring.template piece<7>(); }
-        ++ring.g;
-    }
-    ring.cur = ring.nxt = ring.rd0;
-    __syncthreads();
-    const int64_t n_tiles = (n + 31) >> 5;
-    const int64_t per_round = (int64_t)gridDim.x * NW;
-    const int64_t rounds = (n_tiles + per_round - 1) / per_round;
+    ring.template start<NW>(a, lds3, wave, lane);
+    const Rounds<NW> rounds(n);
     State<H> st;
-    {
-        const unsigned base = ring.rd0;
-        st.aw[0][0].hi = lds16<0>(base); st.aw[0][0].lo = lds16<1024>(base);
-        st.aw[0][1].hi = lds16<PAIR_B>(base); st.aw[0][1].lo = lds16<PAIR_B + 1024>(base);
-        st.aw[1][0].hi = lds16<2 * PAIR_B>(base); st.aw[1][0].lo = lds16<2 * PAIR_B + 1024>(base);
-        st.aw[1][1].hi = lds16<3 * PAIR_B>(base); st.aw[1][1].lo = lds16<3 * PAIR_B + 1024>(base);
-    }
+    st.prime(ring.rd0);
     Tile tl;
     tl.h = h; tl.lane = lane; tl.yrow = nullptr; tl.store = false;
     tl.lane_off = (unsigned)(4 * h * 32 + j) * 4u;
     asm volatile("" : "+v"(tl.lane_off));
-    tl.max0 = lds0 + NRING * CHUNK_B + (unsigned)threadIdx.x * 4u;
+    tl.max0 = lds0 + Lds::maxima_off(a.L) + (unsigned)threadIdx.x * 4u;
     const unsigned bias0 = 0;               // (no bias in the chain)
 #pragma clang loop unroll(disable)
-    for (int64_t round = 0; round < rounds; ++round) {
-        const int64_t tile_raw = (round * gridDim.x + blockIdx.x) * NW + wave;
-        const bool tile_ok = tile_raw < n_tiles;
-        const int64_t tile = tile_ok ? tile_raw : n_tiles - 1;
-        tl.own_tile = tile_ok;
+    for (int64_t round = 0; round < rounds.rounds; ++round) {
+        const int64_t tile = rounds.tile(round, wave, tl.own_tile);
         tl.rows_base = urow(a.rows, tile * a.rows_total);
-        float inv_in;
-        {   // the gradient the chain starts from: H rows of the tile in the D layout, exact column maximum
-            const float *in = urow(tl.rows_base, a.off_in);
-            float mx = 0.0f;
-            float x[NB][16];
-#pragma unroll
-            for (int t = 0; t < NB; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) { x[t][r] = in[(32 * t + frow(r, h)) * 32 + j]; mx = fmaxf(mx, fabsf(x[t][r])); }
-            mx = f2_xmax(mx);
-            float s_in;
-            f2_scales(mx, s_in, inv_in);
-            st.xmax = mx * s_in;
-#pragma unroll
-            for (int b = 0; b < KS; ++b) {
-                float v[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = x[b >> 1][8 * (b & 1) + e] * s_in;
-                f2_split8(v, 1.0f, st.Q[b].hi, st.Q[b].lo);
-            }
-        }
+        // the gradient the chain starts from: H rows of the tile
+        float inv_in = load_column<NB>(urow(tl.rows_base, a.off_in), st, j, h);
         inv_in = run_layer<H, KS, 2, false, true>(ring, st, st.Q, st.P, a, 0, bias0, inv_in, tl);
         int l = 1;
-#pragma clang loop unroll(disable)
-        for (; l + 1 < a.L; l += 2) {
-            inv_in = run_layer<H, KS, 2, true, true>(ring, st, st.P, st.Q, a, l, bias0, inv_in, tl);
-            inv_in = run_layer<H, KS, 2, true, true>(ring, st, st.Q, st.P, a, l + 1, bias0, inv_in, tl);
-        }
-        if (l < a.L) {
-            inv_in = run_layer<H, KS, 2, true, true>(ring, st, st.P, st.Q, a, l, bias0, inv_in, tl);
-#pragma unroll
-            for (int b = 0; b < KS - 4; ++b) st.P[b] = st.Q[b];
-        }
+        inv_in = hidden_walk<H, 2, true>(ring, st, a, l, a.L - 1, bias0, inv_in, tl);
         // the last layer's last two blocks: their rows (the operands they would become have no consumer)
-        {
-            Layer<H, KS, 2, true, true> L{ring, st, st.P, st.Q, 0u, 0.0f, 0.0f, 0.0f, inv_in, 0.0f, 0.0f, 0.0f, nullptr, false, h};
-            L.lane_off = tl.lane_off; L.lane = lane; L.max_addr = 0; L.own_tile = tile_ok;
-            L.template flush_pending<0>(); L.template flush_pending<1>(); L.template flush_pending<2>(); L.template flush_pending<3>();
-            L.template flush_pending<4>(); L.template flush_pending<5>(); L.template flush_pending<6>(); L.template flush_pending<7>();
-            L.template flush_pending<8>(); L.template flush_pending<9>(); L.template flush_pending<10>(); L.template flush_pending<11>();
-            L.template flush_pending<12>(); L.template flush_pending<13>(); L.template flush_pending<14>(); L.template flush_pending<15>();
-        }
+        flush_layer<H, 2, true>(ring, st, inv_in, tl).flush_pending();
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (a.tail != nullptr) {
-        __syncthreads();
-        for (int l = 0; l < a.L; ++l) {
-            if (a.tail_idx[l] < 0) continue;
-            float m = max_s[l * 64 * NW + threadIdx.x];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
-            if (lane == 0) atomicMax(reinterpret_cast<unsigned *>(a.tail + a.tail_idx[l]), __float_as_uint(m));
-        }
-    }
+    publish_maxima<Lds>(a, lds_raw, lane);
+}
+
+// One workgroup of NW waves per CU, at most 256 of them, each wave a tile per round
+int launch_persistent(void (*kern)(FusedArgs, int64_t), int NW, size_t lds_bytes, const char *entry, const char *name, const FusedArgs &f, int64_t n, hipStream_t s)
+{
+    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+    if (e != hipSuccess) { tn::set_error("%s: cannot reserve %zu B of LDS: %s", entry, lds_bytes, hipGetErrorString(e)); return (int)e; }
+    const int64_t n_tiles = (n + 31) / 32;
+    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + NW - 1) / NW, 256));
+    kern<<<dim3((unsigned)bl), dim3(64 * NW), lds_bytes, s>>>(f, n);
+    return tn::check_launch(name);
 }
 
 template <int H>
 int launch_chain(const FusedArgs &f, int64_t n, hipStream_t s)
 {
     constexpr int NW = NWAVES<H, true>;
+    using Lds = FusedLds<H, NW, false, true>;
     // (f.L <= TN_MLP_MAX_LAYERS: ring + maxima table <= 4 x 32 KiB + 12 x 256 x 8 B + 64 B always fit)
-    static_assert(NRING * CHUNK_B + TN_MLP_MAX_LAYERS * 256 * NW + 64 <= LDS_LIMIT_BYTES, "fused chain: LDS");
-    const size_t lds_bytes = (size_t)NRING * CHUNK_B + (size_t)f.L * 256 * NW + 64;
-    auto kern = fused_chain_kernel<H>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_bwd(fused chain): cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + NW - 1) / NW, 256));
-    kern<<<dim3((unsigned)bl), dim3(64 * NW), lds_bytes, s>>>(f, n);
-    return tn::check_launch("fused_chain_kernel");
+    static_assert(Lds::bytes(TN_MLP_MAX_LAYERS) <= LDS_LIMIT_BYTES, "fused chain: LDS");
+    return launch_persistent(fused_chain_kernel<H>, NW, Lds::bytes(f.L), "mlp_bwd(fused chain)", "fused_chain_kernel", f, n, s);
 }
 
 template <int H, bool STASH>
 int launch(const FusedArgs &f, int64_t n, hipStream_t s)
 {
     constexpr int NW = NWAVES<H, !STASH>;
+    using Lds = FusedLds<H, NW, true, STASH>;
     // (f.L <= TN_MLP_MAX_LAYERS: ring + bias table + maxima table always fit)
-    static_assert(NRING * CHUNK_B + TN_MLP_MAX_LAYERS * H * 4 + (STASH ? TN_MLP_MAX_LAYERS * 256 * NW : 0) + 64 <= LDS_LIMIT_BYTES, "fused forward: LDS");
-    const size_t lds_bytes = (size_t)NRING * CHUNK_B + (size_t)f.L * H * 4 + (STASH ? (size_t)f.L * 256 * NW : 0) + 64;
-    auto kern = fused_fwd_kernel<H, STASH>;
-    hipError_t e = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess) { tn::set_error("mlp_fwd(fused): cannot reserve %zu B of LDS: %s", lds_bytes, hipGetErrorString(e)); return (int)e; }
-    const int64_t n_tiles = (n + 31) / 32;
-    const int64_t bl = std::max<int64_t>(1, std::min<int64_t>((n_tiles + NW - 1) / NW, 256));
-    kern<<<dim3((unsigned)bl), dim3(64 * NW), lds_bytes, s>>>(f, n);
-    return tn::check_launch("fused_fwd_kernel");
+    static_assert(Lds::bytes(TN_MLP_MAX_LAYERS) <= LDS_LIMIT_BYTES, "fused forward: LDS");
+    return launch_persistent(fused_fwd_kernel<H, STASH>, NW, Lds::bytes(f.L), "mlp_fwd(fused)", "fused_fwd_kernel", f, n, s);
+}
+
+// bytes of one layer in the stream (the forward's first layer has <= 64 input rows: KS0 k steps), chunks of a whole stack
+constexpr int64_t layer_bytes(int H, bool first) { return (int64_t)(H / 32) * (first ? KS0 : H / 16) * PAIR_B; }
+constexpr int64_t stream_chunks(int H, int L, bool narrow_first) { return (layer_bytes(H, narrow_first) + (L - 1) * layer_bytes(H, false) + CHUNK_B - 1) / CHUNK_B; }
+
+// the arguments of a launch that wants nothing: no inputs, no y, no rows, no maxima
+FusedArgs nothing_wanted()
+{
+    FusedArgs f;
+    f.stream = nullptr; f.bias = nullptr; f.consts = nullptr; f.L = 0; f.n_chunks = 0; f.out_act = TN_ACT_NONE;
+    f.e_rows = nullptr; f.e_rows_total = 0; f.e_off = 0; f.y = nullptr;
+    f.rows = nullptr; f.rows_total = 0; f.out_linear = 0; f.tail = nullptr; f.off_in = 0;
+    for (int i = 0; i < TN_MLP_MAX_LAYERS; ++i) { f.off_out[i] = 0; f.off_bits[i] = 0; f.tail_idx[i] = -1; }
+    return f;
+}
+
+// Stream position i = layer `layer(i)` of the stack, L of them (transpose: as W^T, all H x H): stream, bias and constants placed in the pack
+// area, the pack kernel launched.  -> f: nothing_wanted() with those, L and n_chunks set
+template <class Map>
+int pack_stream(int H, int L, bool transpose, const MlpArgs &a, Map layer, void *pack_area, hipStream_t s, FusedArgs &f)
+{
+    PackArgs p;
+    p.L = L; p.H = H; p.transpose = transpose;
+    int64_t off = 0;
+    for (int i = 0; i < L; ++i) {
+        const int l = layer(i);
+        const bool first = !transpose && i == 0;
+        p.W[i] = a.W[l]; p.B[i] = a.B[l]; p.N[i] = a.N[l]; p.K[i] = first ? a.K0 : a.K[l];
+        p.off[i] = off;
+        off += layer_bytes(H, first);
+    }
+    const int64_t chunks = stream_chunks(H, L, !transpose);
+    p.stream = reinterpret_cast<unsigned char *>(pack_area);
+    p.bias = reinterpret_cast<float *>(p.stream + chunks * CHUNK_B);
+    p.consts = p.bias + (int64_t)L * H;
+    if (off != chunks * CHUNK_B) {          // (H = 128: the first layer is 16 pairs, every H x H layer 32: always whole chunks; kept for other shapes)
+        hipError_t me = hipMemsetAsync(p.stream + off, 0, (size_t)(chunks * CHUNK_B - off), s);
+        if (me != hipSuccess) { tn::set_error("mlp_fwd(fused): memset: %s", hipGetErrorString(me)); return (int)me; }
+    }
+    fused_pack_kernel<<<dim3((unsigned)L, 4), dim3(1024), 0, s>>>(p);
+    if (int rc = tn::check_launch(transpose ? "fused_pack_kernel(chain)" : "fused_pack_kernel")) return rc;
+    f = nothing_wanted();
+    f.stream = p.stream; f.bias = p.bias; f.consts = p.consts; f.L = L; f.n_chunks = (int)chunks;
+    return TN_OK;
 }
 
 }  // namespace
@@ -858,9 +886,7 @@ namespace layers {
 // bytes of the packed stream + bias + constants of a stack (first layer <= 64 input rows, L - 1 layers H -> H)
 __attribute__((visibility("hidden"))) int64_t fused_pack_bytes(int H, int L)
 {
-    const int64_t pairs = (int64_t)(H / 32) * KS0 + (int64_t)(L - 1) * (H / 32) * (H / 16);
-    const int64_t chunks = (pairs + CHUNK_PAIRS - 1) / CHUNK_PAIRS;
-    return chunks * CHUNK_B + (int64_t)L * H * 4 + (int64_t)L * 16 + 256;
+    return stream_chunks(H, L, true) * CHUNK_B + (int64_t)L * H * 4 + (int64_t)L * 16 + 256;
 }
 
 // Inference (spec == nullptr): e_rows = 64 rows x 32 samples per tile, contiguous over the tiles; y [n][H].  Training forward: spec says
@@ -870,30 +896,11 @@ __attribute__((visibility("hidden"))) int launch_fused_fwd_f2(int H, const MlpAr
                                                               hipStream_t s, const FusedStash *spec)
 {
     const int L = spec ? spec->n_run : a.n_layers;
-    PackArgs p;
-    p.L = L; p.H = H; p.transpose = 0;
-    int64_t off = 0;
-    for (int l = 0; l < L; ++l) {
-        p.W[l] = a.W[l]; p.B[l] = a.B[l]; p.N[l] = a.N[l]; p.K[l] = l == 0 ? a.K0 : a.K[l];
-        p.off[l] = off;
-        off += (int64_t)(H / 32) * (l == 0 ? KS0 : H / 16) * PAIR_B;
-    }
-    const int64_t chunks = (off + CHUNK_B - 1) / CHUNK_B;
-    p.stream = reinterpret_cast<unsigned char *>(pack_area);
-    p.bias = reinterpret_cast<float *>(p.stream + chunks * CHUNK_B);
-    p.consts = p.bias + (int64_t)L * H;
-    if (off != chunks * CHUNK_B) {          // (H = 128: the first layer is 16 pairs, every hidden layer 32: always whole chunks; kept for other shapes)
-        hipError_t me = hipMemsetAsync(p.stream + off, 0, (size_t)(chunks * CHUNK_B - off), s);
-        if (me != hipSuccess) { tn::set_error("mlp_fwd(fused): memset: %s", hipGetErrorString(me)); return (int)me; }
-    }
-    fused_pack_kernel<<<dim3((unsigned)L, 4), dim3(1024), 0, s>>>(p);
-    if (int rc = tn::check_launch("fused_pack_kernel")) return rc;
     FusedArgs f;
-    f.stream = p.stream; f.bias = p.bias; f.consts = p.consts; f.L = L; f.n_chunks = (int)chunks; f.out_act = a.out_act;
-    f.e_rows = e_rows; f.e_rows_total = 64; f.e_off = 0; f.y = y;
-    f.rows = nullptr; f.rows_total = 0; f.out_linear = 1; f.tail = nullptr;
-    f.off_in = 0;
-    for (int l = 0; l < TN_MLP_MAX_LAYERS; ++l) { f.off_out[l] = 0; f.off_bits[l] = 0; f.tail_idx[l] = l >= 1 ? l : -1; }
+    if (int rc = pack_stream(H, L, false, a, [](int i) { return i; }, pack_area, s, f)) return rc;
+    f.out_act = a.out_act;
+    f.e_rows = e_rows; f.e_rows_total = 64; f.y = y; f.out_linear = 1;
+    for (int l = 1; l < TN_MLP_MAX_LAYERS; ++l) f.tail_idx[l] = l;
     if (spec == nullptr) return H == 256 ? launch<256, false>(f, n, s) : launch<128, false>(f, n, s);
     f.e_rows_total = spec->rows_total; f.e_off = spec->off_e;
     f.rows = spec->rows; f.rows_total = spec->rows_total; f.out_linear = spec->n_run == a.n_layers ? 1 : 0; f.tail = spec->tail;
@@ -908,26 +915,9 @@ __attribute__((visibility("hidden"))) int launch_fused_chain_f2(int H, const Mlp
 {
     const int L = top;                      // chain positions 0 .. top - 1 = layers top .. 1
     if (L < 1 || L > TN_MLP_MAX_LAYERS) return tn::fail(TN_E_CONFIG, "mlp_bwd(fused chain): nothing to do");
-    PackArgs p;
-    p.L = L; p.H = H; p.transpose = 1;
-    int64_t off = 0;
-    for (int i = 0; i < L; ++i) {
-        const int l = top - i;
-        p.W[i] = a.W[l]; p.B[i] = a.B[l]; p.N[i] = a.N[l]; p.K[i] = a.K[l];
-        p.off[i] = off;
-        off += (int64_t)(H / 32) * (H / 16) * PAIR_B;
-    }
-    const int64_t chunks = off / CHUNK_B;
-    p.stream = reinterpret_cast<unsigned char *>(pack_area);
-    p.bias = reinterpret_cast<float *>(p.stream + chunks * CHUNK_B);
-    p.consts = p.bias + (int64_t)L * H;
-    fused_pack_kernel<<<dim3((unsigned)L, 4), dim3(1024), 0, s>>>(p);
-    if (int rc = tn::check_launch("fused_pack_kernel(chain)")) return rc;
     FusedArgs f;
-    f.stream = p.stream; f.bias = p.bias; f.consts = p.consts; f.L = L; f.n_chunks = (int)chunks; f.out_act = TN_ACT_NONE;
-    f.e_rows = nullptr; f.e_rows_total = 0; f.e_off = 0; f.y = nullptr;
-    f.rows = spec->rows; f.rows_total = spec->rows_total; f.out_linear = 0; f.tail = spec->tail; f.off_in = spec->off_in;
-    for (int i = 0; i < TN_MLP_MAX_LAYERS; ++i) { f.off_out[i] = 0; f.off_bits[i] = 0; f.tail_idx[i] = -1; }
+    if (int rc = pack_stream(H, L, true, a, [top](int i) { return top - i; }, pack_area, s, f)) return rc;
+    f.rows = spec->rows; f.rows_total = spec->rows_total; f.tail = spec->tail; f.off_in = spec->off_in;
     for (int i = 0; i < L; ++i) { f.off_out[i] = spec->off_out[i]; f.off_bits[i] = spec->off_bits[i]; f.tail_idx[i] = spec->tail_idx[i]; }
     return H == 256 ? launch_chain<256>(f, n, s) : launch_chain<128>(f, n, s);
 }
