@@ -112,7 +112,8 @@ int tn_occupancy_stats(const float *grid, int64_t n, float threshold, double *st
  * a1-a4, a7  ray marching + sample packing                    (reference core.py:11-88,158-188)
  * ------------------------------------------------------------------------------------------ */
 enum { TN_MARCH_AABB = 0, TN_MARCH_UNBOUNDED = 1 };
-enum { TN_CONTRACT_AABB = 0, TN_CONTRACT_MIP360_INF = 1, TN_CONTRACT_MIP360_L2 = 2 };
+enum { TN_CONTRACT_AABB = 0, TN_CONTRACT_MIP360_INF = 1, TN_CONTRACT_MIP360_L2 = 2,
+       TN_CONTRACT_NONE = 3 /* tn_normal_frame only: no contraction, J = I */ };
 
 typedef struct tn_sampler_desc {
     int32_t marcher;          /* TN_MARCH_*    (core.py:36-88)                               */
@@ -498,6 +499,56 @@ typedef struct tn_hashgrid_desc {
 int tn_hashgrid_fwd(const tn_hashgrid_desc *desc, const float *x, int64_t x_stride, int64_t n, float *feat, void *stream);
 int tn_hashgrid_bwd(const tn_hashgrid_desc *desc, const float *x, int64_t x_stride, int64_t n, const float *grad_feat,
                     float *grad_table, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Surface normals: the analytic gradient of the density with respect to the sample position, for the two fields that sit directly
+ * in front of the small sigma head (K-Planes, hash grid).  No reference call site: the reference differentiates with respect to
+ * parameters only and renders no normals.  Inference only.
+ * Sigma head (reference models.py:70-76, VanillaOpacityDecoder): y(f) = b2 + sum_j w2_j max(0, h_j), h = W1 f + b1, sigma = exp(y - 1).
+ *   sigma > 0, so -grad sigma / |grad sigma| = -grad y / |grad y|: neither the activation nor sigma is needed.  With
+ *   relu'(h) = [h > 0] (torch's backward: 0 at h == 0):  g = dy/df = W1^T (w2 . [h > 0]), an F-vector per sample.
+ * Contracted frame: grad_x y = sum_c g_c df_c/dx, x = columns 0..2 of a row of `x_stride` floats, as the field's forward reads them.
+ *   K-Planes: f[s C + c] = P0(x0,x1) P1(x0,x2) P2(x1,x2) per scale -> the product rule over the three planes.  A plane's value and cell
+ *     are the forward's (same ix, iy, floor cell, zero padding; u indexes W, v indexes H).  With the cell's texels t_nw, t_ne, t_sw, t_se
+ *     (an out-of-bounds tap counts as 0) and fx = ix - floor(ix), gx = 1 - fx, fy, gy likewise:
+ *       dP/du = (W - 1)/2 * ((t_ne - t_nw) gy + (t_se - t_sw) fy),    dP/dv = (H - 1)/2 * ((t_sw - t_nw) gx + (t_se - t_ne) fx)
+ *     -- the derivative inside the cell the forward chose, right-sided at a node.
+ *   Hash grid: per level, p_a, i_a, f_a as defined above;  dfeat/dx_a = (N_l / 2) * sum over the 8 corners of (+1 for the upper corner
+ *     on axis a, -1 for the lower) * (the weights of the other two axes) * table[...];  0 on an axis where the clamp acts, i.e. where
+ *     fmaf(x, N_l/2, N_l/2) is < 0, > N_l or NaN.
+ * World frame: v = -J^T grad_x y, J = d x / d X the Jacobian of the contraction, recovered from the contracted x alone:
+ *   TN_CONTRACT_NONE        J = I
+ *   TN_CONTRACT_AABB        J = diag(2 / (hi - lo))
+ *   TN_CONTRACT_MIP360_INF / _L2 (p = inf / 2): u = 2 x, s = |u|_p;  s <= 1: J = I / 2;  s >= 2 or not finite: v = 0;  otherwise
+ *     m = 1 / (2 - s), X = (m / s) u,  J_ij = ((2/m - 1/m^2) delta_ij + X_i (2/m^3 - 2/m^2) dm/dX_j) / 2,
+ *     dm/dX_j = sign(X_k) delta_jk with k the lowest axis with |X_k| = m (p = inf), = X_j / m (p = 2).
+ * Outputs: normals [n,3] = v / |v| when |v| is finite and > 0, else (0,0,0) -- unit, pointing from dense to empty; also (0,0,0) for a
+ *   row whose x is not finite.  grad [n,3] = grad_x y before the frame.  Either may be NULL, not both.  gate [n] (optional; the renderer
+ *   passes the volume-rendering weights): a row whose gate is 0 gets zeros in both outputs, and a 32-row tile whose gates are all 0
+ *   reads no texel / table entry.  fp32 throughout, no fp16 operand splits whatever head->flags says (a ReLU bit that moved with the
+ *   matrix mode would make a normal depend on a flag); head->flags and head->out_activation are ignored, b2 is not read.
+ * One launch per call.  TN_E_CONFIG: a head that is not 2 layers with dims {F, 64, 1}, in_dim F, TN_ENC_NONE, F the field's feature
+ *   width; an unknown frame, or an AABB frame without finite hi > lo; K-Planes: channels not 4, 8, 16 or 32 (tn_kplanes_fwd's widths
+ *   and 4), n_scales out of range or a missing plane (all three planes of every scale must be present); hash grid: as tn_hashgrid_fwd.
+ *   TN_E_SIZE: n < 0, x_stride < 3, a bad plane size.  TN_E_NULL: a null descriptor, head parameter or x, or normals == grad == NULL.
+ *   TN_E_ALIGN: planes / table not 16-byte aligned.  frame == NULL is the TN_CONTRACT_NONE frame.  Every argument is checked before the
+ *   first HIP call; n == 0 returns TN_OK without a launch (after the descriptor checks).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct tn_normal_frame {
+    int32_t contraction;      /* TN_CONTRACT_* (TN_CONTRACT_NONE included) */
+    int32_t reserved;
+    float aabb[6];            /* TN_CONTRACT_AABB: lo xyz, hi xyz */
+} tn_normal_frame;
+int tn_kplanes_normals(const tn_kplanes_desc *f, const float *x, int64_t x_stride, int64_t n, const tn_mlp_desc *head,
+                       const tn_normal_frame *frame, const float *gate, float *normals, float *grad, void *stream);
+int tn_hashgrid_normals(const tn_hashgrid_desc *f, const float *x, int64_t x_stride, int64_t n, const tn_mlp_desc *head,
+                        const tn_normal_frame *frame, const float *gate, float *normals, float *grad, void *stream);
+/* Ray normal: N_r = sum_k w_k n_k over the ray's samples (weights [N], normals [N,3]: the weights the forward composited with and
+ * tn_*_normals' output), out[r] = N_r / |N_r|, or 0 when the norm is 0 or not finite; rays without samples get 0.  One wave per ray,
+ * the lane order and reduction tree of tn_ray_maps' first pass; info must be 8-byte aligned.  n_rays == 0 returns TN_OK without a
+ * launch.  No reference call site. */
+int tn_ray_normals(const float *weights, const float *normals, const int32_t *info, int64_t n_rays, float *out, void *stream);
+
 
 /* north star: "the K-Planes bilinear grid sample ... fused into the same launch" as the persistent MLP.  tn_kplanes_fwd +
  * tn_mlp_fwd_stash_pair in ONE launch (reference call chain core.py:239-249 -> models.py:153-163 -> models.py:70-89): every

@@ -19,6 +19,7 @@ TN_KPLANES_MAX_SCALES = 4
 
 MARCH_AABB, MARCH_UNBOUNDED = 0, 1
 CONTRACT_AABB, CONTRACT_MIP360_INF, CONTRACT_MIP360_L2 = 0, 1, 2
+CONTRACT_NONE = 3                      # tn_normal_frame only: no contraction (TN_CONTRACT_NONE)
 ACT_NONE, ACT_EXP_M1, ACT_SIGMOID, ACT_EXP = 0, 1, 2, 3
 ENC_NONE, ENC_POSENC, ENC_DIR_CAT, ENC_AUX_CAT = 0, 1, 2, 3
 DIST_LINEAR, DIST_UNBOUNDED = 0, 1          # tn_distortion_fwd / tn_distortion_bwd: the warp of t (TN_DIST_*)
@@ -118,6 +119,11 @@ class HashGridDesc(C.Structure):
         ("entries", C.c_int64 * TN_HASHGRID_MAX_LEVELS), ("offset", C.c_int64 * TN_HASHGRID_MAX_LEVELS),
         ("table", C.c_void_p),
     ]
+
+
+class NormalFrame(C.Structure):
+    """tn_normal_frame: the contraction whose Jacobian takes a density gradient to the world frame (tn_kplanes_normals / tn_hashgrid_normals)"""
+    _fields_ = [("contraction", C.c_int32), ("reserved", C.c_int32), ("aabb", C.c_float * 6)]
 
 
 LENS_PINHOLE, LENS_OPENCV, LENS_FISHEYE = 0, 1, 2      # tn_camera_table.model (TN_LENS_*)

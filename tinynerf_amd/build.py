@@ -37,6 +37,7 @@ SOURCES = {
     "cameras.hip": FAST,
     "points.hip": FAST,
     "kplanes.hip": FAST + ["-munsafe-fp-atomics"],
+    "normals.hip": FAST,
     "cobafa.hip": STRICT + ["-munsafe-fp-atomics"],   # sawtooth warp x (res-1): an fma in f*x - floor moves taps
     "hashgrid.hip": FAST + ["-munsafe-fp-atomics"],
     "mlp.hip": FAST,

@@ -458,6 +458,91 @@ class RayDistortion(torch.autograd.Function):
         return g_w, None, None, None, None, None, None
 
 
+def normal_frame(contraction: Optional[Contraction]) -> L.NormalFrame:
+    """``tn_normal_frame`` of a contraction (``None``: the none frame, J = I) for ``sample_normals`` / ``NerfRenderer.normal_frame``"""
+    frame = L.NormalFrame(contraction=L.CONTRACT_NONE)
+    if contraction is None:
+        return frame
+    if isinstance(contraction, ContractionMip360):
+        frame.contraction = contraction._code()
+    elif isinstance(contraction, ContractionAABB):
+        frame.contraction = L.CONTRACT_AABB
+        vals = _host_floats(contraction.aabb)
+        for i in range(6):
+            frame.aabb[i] = vals[i]
+    else:
+        raise TypeError(f"no normal frame for {type(contraction).__name__}")
+    return frame
+
+
+@torch.no_grad()
+def sample_normals(renderer: "NerfRenderer", packed: torch.Tensor, gate: Optional[torch.Tensor] = None, return_grad: bool = False):
+    """Unit world-frame surface normals ``[n,3]`` of packed samples (columns 0..2 of ``packed`` [n, >= 3]: the contracted position): the
+    negated, normalised gradient of the density with respect to the position, analytically through the field and the sigma head
+    (``tn_kplanes_normals`` / ``tn_hashgrid_normals``), taken to the world frame by ``renderer.normal_frame``.  ``gate`` [n]
+    (the renderer passes the weights): rows whose gate is 0 get zeros.  ``return_grad``: ``(normals, grad)`` with ``grad`` [n,3] the
+    gradient of the head's pre-activation in the contracted frame.  Inference only; K-Planes and hash-grid fields in front of a
+    ``VanillaOpacityDecoder`` -- anything else raises ``NotImplementedError``."""
+    from . import models as M
+    fm, sd = renderer.feature_module, renderer.sigma_decoder
+    if not isinstance(fm, (M.KPlanesFeatureField, M.HashGridFeatureField)):
+        raise NotImplementedError(f"sample_normals: no analytic density gradient through {type(fm).__name__} (K-Planes and hash-grid fields only: "
+                                  "the 10-layer Vanilla and Cobafa stacks are not differentiated with respect to position)")
+    if not isinstance(sd, M.VanillaOpacityDecoder):
+        raise NotImplementedError(f"sample_normals: the sigma decoder must be a VanillaOpacityDecoder, not {type(sd).__name__}")
+    params = sd.net.params()
+    F = int(fm.feature_dim)
+    if len(params) != 4 or tuple(params[0].shape) != (64, F) or tuple(params[2].shape) != (1, 64):
+        raise NotImplementedError(f"sample_normals: the sigma head must be {F} -> 64 -> 1")
+    if packed.dim() != 2 or packed.size(1) < 3:
+        raise RuntimeError("sample_normals: packed must be [n, >= 3] (contracted xyz first)")
+    x = packed if packed.dtype == torch.float32 else packed.float()
+    if x.stride(1) != 1 or (x.size(0) > 1 and x.stride(0) < 3):
+        x = x.contiguous()
+    n = x.size(0)
+    tensors = [x] + [p.detach() for p in params]
+    if gate is not None:
+        gate = _f32c(gate.detach()).reshape(-1)
+        if gate.numel() != n:
+            raise RuntimeError("sample_normals: gate must hold one value per sample")
+        tensors.append(gate)
+    dev = x.device
+    if not all(t.is_cuda for t in tensors):
+        raise RuntimeError("tinynerf_amd: tensor must be a CUDA (HIP) tensor -- there is no CPU path")
+    normals = torch.empty((n, 3), device=dev)
+    grad = torch.empty((n, 3), device=dev) if return_grad else None
+    if n > 0:
+        head = M._mlp_desc([p.detach() for p in params], F, L.ENC_NONE, 0, L.ACT_EXP_M1, None)
+        frame = renderer.normal_frame if renderer.normal_frame is not None else L.NormalFrame(contraction=L.CONTRACT_NONE)
+        stride = x.stride(0) if n > 1 else x.size(1)
+        if isinstance(fm, M.KPlanesFeatureField):
+            desc, keep = M._kplanes_desc([p.detach() for p in fm.plane_tensors()])
+            name = "tn_kplanes_normals"
+        else:
+            table = fm.table.detach()
+            if not table.is_contiguous() or table.dtype != torch.float32:
+                raise RuntimeError("tinynerf_amd: the hash grid's table must be a contiguous fp32 tensor")
+            desc, keep = M._hashgrid_desc(fm.plan, table.size(1), table), [table]
+            name = "tn_hashgrid_normals"
+        L.call(name, dev, C.byref(desc), L.ptr(x), C.c_int64(stride), C.c_int64(n), C.byref(head), C.byref(frame), L.ptr(gate),
+               L.ptr(normals), L.ptr(grad))
+        del keep
+    return (normals, grad) if return_grad else normals
+
+
+@torch.no_grad()
+def ray_normals(weights: torch.Tensor, normals: torch.Tensor, packing_info: torch.Tensor) -> torch.Tensor:
+    """``[R,3]``: the weighted sum of every ray's sample normals, normalised (0 where it vanishes or the ray is empty) -- ``tn_ray_normals``"""
+    _check_info(packing_info)
+    R = packing_info.size(0)
+    out = torch.zeros((R, 3), device=packing_info.device)
+    if R > 0 and weights.numel() > 0:
+        w, nrm, info = _f32c(weights.detach()), _f32c(normals), packing_info.contiguous()
+        dev = L.require_cuda(w, nrm, info)
+        L.call("tn_ray_normals", dev, L.ptr(w), L.ptr(nrm), L.ptr(info), C.c_int64(R), L.ptr(out))
+    return out
+
+
 class NerfRenderer(torch.nn.Module):
     def __init__(
         self,
@@ -478,6 +563,9 @@ class NerfRenderer(torch.nn.Module):
         self.reuse_buffers = False             # harness option: capacity-based scratch arena (fused.Arena)
         # render_with_distortion: (warp, near, range) of the marcher that made the samples (distortion_warp(marcher)); the trainer sets it
         self.distortion_warp: Optional[Tuple[int, float, float]] = None
+        # render_maps(normals=True) / sample_normals: the frame of the contraction that made the samples (normal_frame(contraction));
+        # None = no contraction.  The trainer sets it.
+        self.normal_frame: Optional[L.NormalFrame] = None
         assert hasattr(self.feature_module, "feature_dim"), "feature module requires a feature_dim attribute"
 
     def _bg(self, device: torch.device) -> Optional[torch.Tensor]:
@@ -578,13 +666,16 @@ class NerfRenderer(torch.nn.Module):
         packing_info: torch.Tensor,  # [n_rays, 2]
         t: torch.Tensor,  # [n_samples], RayProvider(..., return_t=True)
         early_termination_threshold: float = 1e-4,
+        normals: bool = False,
     ) -> dict:
         """Inference: ``forward``'s colour plus per-ray maps of the weights it composited with, as a dict of
         ``rgb [R,3]`` (bit-identical to ``forward``), ``opacity [R]`` (sum of the weights), ``depth [R]`` (expected
         depth given a hit: sum w t / opacity) and ``median_depth [R]`` (t where the weights' prefix reaches half the
         opacity); rays with opacity 0 get depth 0.  Same dispatch as ``forward`` (fused nodes or the module path);
         the weights are handed out by that forward, not recomputed (``tn_ray_maps``).  The maps carry no gradient:
-        call it under ``torch.no_grad()`` when parameters require grad."""
+        call it under ``torch.no_grad()`` when parameters require grad.  ``normals``: the dict also holds ``normal [R,3]``, the
+        normalised weighted sum of the samples' surface normals (``sample_normals`` gated by the handed-out weights, then
+        ``tn_ray_normals``; 0 for rays with opacity 0) -- a pass after the forward; every other entry keeps its bits."""
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             raise RuntimeError("NerfRenderer.render_maps is inference only: call it under torch.no_grad()")
         if t.dim() != 1 or t.size(0) != packed_samples.size(0):
@@ -600,4 +691,11 @@ class NerfRenderer(torch.nn.Module):
         if weights is None:
             weights = torch.zeros(0, device=packed_samples.device)
         opacity, depth, median = self._maps(weights.detach(), packing_info, t)
-        return {"rgb": rgb, "opacity": opacity, "depth": depth, "median_depth": median}
+        out = {"rgb": rgb, "opacity": opacity, "depth": depth, "median_depth": median}
+        if normals:
+            if weights.numel() > 0:
+                out["normal"] = ray_normals(weights, sample_normals(self, packed_samples, gate=weights), packing_info)
+            else:
+                sample_normals(self, packed_samples[:0])          # (still says so when the field has no normals)
+                out["normal"] = torch.zeros((packing_info.size(0), 3), device=packed_samples.device)
+        return out

@@ -5,48 +5,14 @@
 // Mapping, both directions: lane = packed sample (consecutive lanes are neighbours along a ray), blockIdx.y = level.  The hardware
 // hands out workgroups x-fastest, so the workgroups in flight at any time work on ONE level (two at a boundary) and that level's table
 // -- 4 MB at F = 2, T = 2^19 -- is what the caches hold, not all sixteen.  An entry is one 8- or 16-byte load.
-#include "tn_common.h"
+#include "hashgrid_device.h"
 #include <stdlib.h>
 #include <string.h>
 
 namespace {
 
-struct HgArgs {
-    int n_levels, feat_dim;
-    int res[TN_HASHGRID_MAX_LEVELS], hashed[TN_HASHGRID_MAX_LEVELS];
-    uint32_t mask[TN_HASHGRID_MAX_LEVELS];          // hashed: T - 1
-    int64_t offset[TN_HASHGRID_MAX_LEVELS];         // entries
-    const float *table;
-    float *gtable;
-};
-
-template <int F> struct EntryT;
-template <> struct EntryT<2> { typedef float2 type; };
-template <> struct EntryT<4> { typedef float4 type; };
-
-template <int F> __device__ __forceinline__ void unpack(const typename EntryT<F>::type &e, float (&v)[F]);
-template <> __device__ __forceinline__ void unpack<2>(const float2 &e, float (&v)[2]) { v[0] = e.x; v[1] = e.y; }
-template <> __device__ __forceinline__ void unpack<4>(const float4 &e, float (&v)[4]) { v[0] = e.x; v[1] = e.y; v[2] = e.z; v[3] = e.w; }
-template <int F> __device__ __forceinline__ typename EntryT<F>::type pack(const float (&v)[F]);
-template <> __device__ __forceinline__ float2 pack<2>(const float (&v)[2]) { return make_float2(v[0], v[1]); }
-template <> __device__ __forceinline__ float4 pack<4>(const float (&v)[4]) { return make_float4(v[0], v[1], v[2], v[3]); }
-
-// cell and fractions of one axis: ONE fused rounding, then a clamp that sends a NaN to 0 and keeps every read inside the table
-__device__ __forceinline__ void axis_cell(float xv, int N, int &i, float &f)
-{
-    const float nf = (float)N, h = 0.5f * nf;        // exact: N <= 2^24
-    float p = fmaf(xv, h, h);
-    p = p > 0.0f ? p : 0.0f;                         // NaN > 0 is false
-    p = p < nf ? p : nf;
-    const int ip = (int)p;
-    i = ip < N - 1 ? ip : N - 1;
-    f = p - (float)i;                                // exact in fp32
-}
-
-__device__ __forceinline__ uint32_t node_index(bool hashed, uint32_t mask, uint32_t S, uint32_t ix, uint32_t iy, uint32_t iz)
-{
-    return hashed ? ((ix ^ (iy * 2654435761u) ^ (iz * 805459861u)) & mask) : ix + S * (iy + S * iz);
-}
+using tn::HgArgs;
+template <int F> using EntryT = tn::HgEntry<F>;
 
 // MERGE (backward only): lanes of a wave that follow each other INSIDE ONE CELL (samples of a ray on a coarse level) share all eight
 // entries.  Their contributions are summed towards the run's first lane with a segmented shuffle reduction and that lane alone issues
@@ -67,14 +33,14 @@ __global__ __launch_bounds__(256) void hashgrid_kernel(HgArgs a, const float *__
     int c0[3];
     float f[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) axis_cell(x[r * x_stride + c], N, c0[c], f[c]);
+    for (int c = 0; c < 3; ++c) tn::hg_axis_cell(x[r * x_stride + c], N, c0[c], f[c]);
     const float wx[2] = {1.0f - f[0], f[0]}, wy[2] = {1.0f - f[1], f[1]}, wz[2] = {1.0f - f[2], f[2]};
     uint32_t idx[8];
     float w[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const int dx = k & 1, dy = (k >> 1) & 1, dz = k >> 2;
-        idx[k] = node_index(hashed, mask, S, (uint32_t)(c0[0] + dx), (uint32_t)(c0[1] + dy), (uint32_t)(c0[2] + dz));
+        idx[k] = tn::hg_node_index(hashed, mask, S, (uint32_t)(c0[0] + dx), (uint32_t)(c0[1] + dy), (uint32_t)(c0[2] + dz));
         w[k] = wx[dx] * wy[dy] * wz[dz];
     }
     if constexpr (!BWD) {
@@ -89,16 +55,16 @@ __global__ __launch_bounds__(256) void hashgrid_kernel(HgArgs a, const float *__
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             float v[F];
-            unpack<F>(e[k], v);
+            tn::hg_unpack<F>(e[k], v);
 #pragma unroll
             for (int c = 0; c < F; ++c) acc[c] = fmaf(w[k], v[c], acc[c]);
         }
-        *reinterpret_cast<entry_t *>(feat + i * FD + l * F) = pack<F>(acc);
+        *reinterpret_cast<entry_t *>(feat + i * FD + l * F) = tn::hg_pack<F>(acc);
     } else {
         float g[F];
         {
             entry_t ge = *reinterpret_cast<const entry_t *>(gfeat + r * FD + l * F);
-            unpack<F>(ge, g);
+            tn::hg_unpack<F>(ge, g);
         }
         float *gt = a.gtable + a.offset[l] * F;
         bool issue = valid;
@@ -140,37 +106,7 @@ __global__ __launch_bounds__(256) void hashgrid_kernel(HgArgs a, const float *__
     }
 }
 
-int make_args(const tn_hashgrid_desc *d, HgArgs &a)
-{
-    TN_REQUIRE(d, TN_E_NULL, "hashgrid: null descriptor");
-    TN_REQUIRE(d->n_levels >= 1 && d->n_levels <= TN_HASHGRID_MAX_LEVELS, TN_E_CONFIG, "hashgrid: n_levels must be in [1, 16]");
-    TN_REQUIRE(d->features == 2 || d->features == 4, TN_E_CONFIG, "hashgrid: features must be 2 or 4");
-    a.n_levels = d->n_levels;
-    a.feat_dim = d->n_levels * d->features;
-    for (int l = 0; l < d->n_levels; ++l) {
-        TN_REQUIRE(d->res[l] >= 1 && d->res[l] <= (1 << 24), TN_E_CONFIG, "hashgrid: a level's resolution must be in [1, 2^24]");
-        const int64_t e = d->entries[l];
-        if (d->hashed[l]) {
-            TN_REQUIRE(e >= 1 && e <= (1ll << 32) && (e & (e - 1)) == 0, TN_E_CONFIG,
-                       "hashgrid: a hashed level's entries must be a power of two (<= 2^32)");
-            a.mask[l] = (uint32_t)(e - 1);
-        } else {
-            const int64_t s = (int64_t)d->res[l] + 1;
-            TN_REQUIRE(s <= 1290 && e >= s * s * s, TN_E_CONFIG, "hashgrid: a dense level needs entries >= (res + 1)^3 (< 2^31)");
-            a.mask[l] = 0;
-        }
-        TN_REQUIRE(d->offset[l] >= 0 && d->offset[l] <= (1ll << 40), TN_E_CONFIG, "hashgrid: bad level offset");
-        for (int m = 0; m < l; ++m)
-            TN_REQUIRE(d->offset[l] + e <= d->offset[m] || d->offset[m] + d->entries[m] <= d->offset[l], TN_E_CONFIG,
-                       "hashgrid: levels overlap in the table");
-        a.res[l] = d->res[l]; a.hashed[l] = d->hashed[l] ? 1 : 0; a.offset[l] = d->offset[l];
-    }
-    TN_REQUIRE(d->table, TN_E_NULL, "hashgrid: null table");
-    TN_REQUIRE(((uintptr_t)d->table & 15) == 0, TN_E_ALIGN, "hashgrid: table must be 16-byte aligned");
-    a.table = d->table;
-    a.gtable = nullptr;
-    return TN_OK;
-}
+inline int make_args(const tn_hashgrid_desc *d, HgArgs &a) { return tn::hg_make_args(d, a); }
 
 // TN_HASHGRID_SCATTER=plain / merged in the environment: A/B of the two scatter forms (LABNOTES); anything else: the default
 bool merged_scatter()

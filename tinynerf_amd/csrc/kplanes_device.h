@@ -50,6 +50,24 @@ __device__ __forceinline__ PlaneTaps plane_taps(float u, float v, int H, int W, 
     return t;
 }
 
+// Position of a point inside the cell plane_taps chooses: the factors of its four weights, w = gx gy, fx gy, gx fy, fx fy, which the
+// density gradient (normals.hip) differentiates.  The first six lines ARE plane_taps' -- the same operations under the same pins, so
+// the same ix, iy and floor cell -- kept as a function of its own so that plane_taps, and with it every kernel that inlines it, compiles
+// to the code it compiled to before; tests/test_hip_normals.py holds the two together at nodes and cell faces.
+struct PlaneCell {
+    float fx, fy, gx, gy;
+};
+
+__device__ __forceinline__ PlaneCell plane_cell(float u, float v, int H, int W) {
+    float u1 = u + 1.0f, v1 = v + 1.0f;
+    asm volatile("" : "+v"(u1), "+v"(v1));
+    float ix = (u1 * 0.5f) * (float)(W - 1);
+    float iy = (v1 * 0.5f) * (float)(H - 1);
+    asm volatile("" : "+v"(ix), "+v"(iy));
+    const float x0f = floorf(ix), y0f = floorf(iy);
+    return {ix - x0f, iy - y0f, (x0f + 1.0f) - ix, (y0f + 1.0f) - iy};
+}
+
 // interpolate NV float4 groups (channels c0 .. c0+4*NV) of one plane.  All 4*NV loads are unconditional (an
 // out-of-bounds tap reads texel 0 with weight 0): a load under `if (in bounds)` has to be waited for at the end of
 // that branch, which serialises the four taps' L2 latencies instead of overlapping all loads of a plane.

@@ -348,6 +348,31 @@ __global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void ray_maps_kernel(
     }
 }
 
+// Ray normal: N = sum w_k n_k in the order of ray_maps_kernel's first pass (for_lane_samples, tn::wave_sum), then N / |N| taken
+// relative to the largest component (no overflow or underflow of the squares); 0 when |N| is 0 or not finite.
+__global__ __launch_bounds__(WAVES_PER_BLOCK * 64) void ray_normals_kernel(
+    const float *__restrict__ weights, const float *__restrict__ normals, const int32_t *__restrict__ info, int64_t n_rays,
+    float *__restrict__ out)
+{
+    const int lane = tn::lane_id();
+    const int64_t ray = wave_ray_index();
+    if (ray >= n_rays) return;
+    const WaveRay r = read_ray(info, ray);
+    float a = 0.f, b = 0.f, c = 0.f;
+    for_lane_samples(r, lane, [&](int64_t i) {
+        const float w = weights[i];
+        a += w * normals[3 * i]; b += w * normals[3 * i + 1]; c += w * normals[3 * i + 2];
+    });
+    a = tn::wave_sum(a); b = tn::wave_sum(b); c = tn::wave_sum(c);
+    if (lane == 0) {
+        const float mx = fmaxf(fmaxf(fabsf(a), fabsf(b)), fabsf(c));
+        const bool ok = mx > 0.f && mx < __builtin_inff() && a == a && b == b && c == c;
+        const float u = a / mx, v = b / mx, w = c / mx;
+        const float len = sqrtf(u * u + v * v + w * w);
+        out[3 * r.ray] = ok ? u / len : 0.f; out[3 * r.ray + 1] = ok ? v / len : 0.f; out[3 * r.ray + 2] = ok ? w / len : 0.f;
+    }
+}
+
 // Distortion loss of Mip-NeRF 360 on packed rays.  For ray r with weights w_k, normalised positions m_k and widths d_k
 //   L = sum_i sum_j w_i w_j |m_i - m_j| + (1/3) sum_i w_i^2 d_i
 // m increases along a ray, so with the exclusive prefixes W_<i = sum_{j<i} w_j and M_<i = sum_{j<i} w_j m_j
@@ -609,6 +634,15 @@ extern "C" int tn_ray_maps(const float *weights, const float *t_values, const in
     TN_REQUIRE(((uintptr_t)info & 7) == 0, TN_E_ALIGN, "tn_ray_maps: info must be 8-byte aligned");
     return launch_waves("ray_maps_kernel", ray_maps_kernel, ray_blocks(n_rays), stream, weights, t_values, info, n_rays, opacity, depth,
                         median_depth);
+}
+
+extern "C" int tn_ray_normals(const float *weights, const float *normals, const int32_t *info, int64_t n_rays, float *out, void *stream)
+{
+    TN_REQUIRE(n_rays >= 0, TN_E_SIZE, "tn_ray_normals: negative size");
+    if (n_rays == 0) return TN_OK;
+    TN_REQUIRE(weights && normals && info && out, TN_E_NULL, "tn_ray_normals: null pointer");
+    TN_REQUIRE(((uintptr_t)info & 7) == 0, TN_E_ALIGN, "tn_ray_normals: info must be 8-byte aligned");
+    return launch_waves("ray_normals_kernel", ray_normals_kernel, ray_blocks(n_rays), stream, weights, normals, info, n_rays, out);
 }
 
 extern "C" int tn_weights_fwd(const float *sigmas, const float *steps, const int32_t *info, float threshold,

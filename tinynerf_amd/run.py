@@ -25,7 +25,7 @@ import torch
 
 from . import _lib as L
 from .core import (ContractionAABB, ContractionMip360, NerfRenderer, OccupancyGrid, RayMarcherAABB,
-                   RayMarcherUnbounded, RayProvider, distortion_warp)
+                   RayMarcherUnbounded, RayProvider, distortion_warp, normal_frame)
 from .optim import FusedAdam
 from .models import (CobafaFeatureField, HashGridFeatureField, KPlanesFeatureField, VanillaColorDecoder, VanillaFeatureMLP,
                      VanillaOpacityDecoder)
@@ -190,6 +190,7 @@ class Trainer:
             raise ValueError("TrainConfig.method = 'hashgrid' is single-GPU for now: the table's gradient (49 MB at the default size) "
                              "has no exchange of its own yet")
         self.renderer.distortion_warp = distortion_warp(self.ray_provider.ray_marcher)
+        self.renderer.normal_frame = normal_frame(self.ray_provider.contraction)
         params = list(self.renderer.parameters())
         for p in params:                                # grads keep the parameter's (channels_last) layout
             p.grad = torch.zeros_like(p)
@@ -838,8 +839,11 @@ class Trainer:
 
     # ------------------------------------------------------------------ inference (run.py:15-50)
     @torch.no_grad()
-    def render_rays(self, rays_o: torch.Tensor, rays_d: torch.Tensor, batch_size: Optional[int] = None, maps: bool = False):
-        """rgb [R,3]; with ``maps`` the dict of ``NerfRenderer.render_maps`` (rgb [R,3], opacity, depth, median_depth [R])"""
+    def render_rays(self, rays_o: torch.Tensor, rays_d: torch.Tensor, batch_size: Optional[int] = None, maps: bool = False,
+                    normals: bool = False):
+        """rgb [R,3]; with ``maps`` the dict of ``NerfRenderer.render_maps`` (rgb [R,3], opacity, depth, median_depth [R]); with
+        ``normals`` (implies ``maps``) that dict also holds ``normal [R,3]``, the unit world-frame surface normal of every ray"""
+        maps = maps or normals
         self.renderer.eval()
         # rays are independent: the chunk size does not change a single output bit.  The reference walks an image in chunks of
         # the training batch size (run.py:35-43: 625 calls per 800x800 image), which makes every launch tiny: 139 ms per
@@ -849,8 +853,9 @@ class Trainer:
             parts = []
             for k in range(0, rays_o.size(0), bs):
                 samples, info, t = self.ray_provider(rays_o[k:k + bs], rays_d[k:k + bs], training=False, return_t=True)
-                parts.append(self.renderer.render_maps(samples, info, t))
-            return {key: torch.cat([p[key] for p in parts], 0) for key in ("rgb", "opacity", "depth", "median_depth")}
+                parts.append(self.renderer.render_maps(samples, info, t, normals=True) if normals else self.renderer.render_maps(samples, info, t))
+            keys = ("rgb", "opacity", "depth", "median_depth") + (("normal",) if normals else ())
+            return {key: torch.cat([p[key] for p in parts], 0) for key in keys}
         out = []
         for k in range(0, rays_o.size(0), bs):
             samples, info = self.ray_provider(rays_o[k:k + bs], rays_d[k:k + bs], training=False)
@@ -870,20 +875,22 @@ class EvalMetrics:
 
 @torch.no_grad()
 def infer(trainer: "Trainer", dataset, indices: List[int], folder=None, name: str = "render", batch_size: Optional[int] = None,
-          maps: bool = False):
+          maps: bool = False, normals: bool = False):
     """Render whole images (run.py:15-50); PNGs are written when `folder` is given.
 
     ``maps``: each entry of the result is the dict of ``Trainer.render_rays(maps=True)`` shaped as the image (rgb [H,W,3],
     opacity / depth / median_depth [H,W]) instead of the image alone, and with `folder` these files are written as well:
     ``{name}_depth_{i:04d}.png`` (16-bit grayscale, expected depth / the image's largest expected depth),
     ``{name}_opacity_{i:04d}.png`` (16-bit grayscale, opacity in [0, 1]) and ``{name}_maps_{i:04d}.npz`` (float32 depth,
-    median_depth, opacity and the PNG's depth_scale)."""
+    median_depth, opacity and the PNG's depth_scale).  ``normals`` (implies ``maps``): the dicts also hold ``normal [H,W,3]``, and with
+    `folder` ``{name}_normal_{i:04d}.png`` (8-bit RGB, round(255 (n + 1) / 2)) is written and the npz carries ``normal``."""
+    maps = maps or normals
     out = []
     for i in indices:
         item = dataset[i]
         o, d = item["rays_o"].reshape(-1, 3).to(trainer.device), item["rays_d"].reshape(-1, 3).to(trainer.device)
         hw = item["rays_o"].shape[:-1]
-        res = trainer.render_rays(o, d, batch_size, maps=maps)
+        res = trainer.render_rays(o, d, batch_size, maps=maps, normals=True) if normals else trainer.render_rays(o, d, batch_size, maps=maps)
         if maps:
             res = {k: v.reshape(*hw, *v.shape[1:]) for k, v in res.items()}
             img = res["rgb"]
@@ -901,7 +908,7 @@ def infer(trainer: "Trainer", dataset, indices: List[int], folder=None, name: st
 def _save_maps(res: Dict[str, torch.Tensor], folder, name: str, i: int) -> None:
     import numpy as np
     from PIL import Image
-    host = {k: res[k].float().cpu().numpy() for k in ("depth", "median_depth", "opacity")}
+    host = {k: res[k].float().cpu().numpy() for k in ("depth", "median_depth", "opacity") + (("normal",) if "normal" in res else ())}
     scale = float(host["depth"].max()) if host["depth"].size else 0.0
 
     def png16(x: "np.ndarray", path) -> None:
@@ -909,6 +916,8 @@ def _save_maps(res: Dict[str, torch.Tensor], folder, name: str, i: int) -> None:
 
     png16(host["depth"] / scale if scale > 0 else host["depth"], folder / f"{name}_depth_{i:04d}.png")
     png16(host["opacity"], folder / f"{name}_opacity_{i:04d}.png")
+    if "normal" in host:
+        Image.fromarray(np.round(255.0 * (np.clip(host["normal"], -1.0, 1.0) + 1.0) / 2.0).astype(np.uint8)).save(folder / f"{name}_normal_{i:04d}.png")
     np.savez(folder / f"{name}_maps_{i:04d}.npz", depth_scale=np.float32(scale), **host)
 
 
@@ -927,15 +936,20 @@ def evaluate(dataset, rendered: List[torch.Tensor], indices: List[int], ssim: bo
 
 def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=None, eval_every: Optional[int] = None,
           eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
-          render_maps: bool = False, ssim: bool = False, pointcloud: int = 0, pointcloud_crop=None):
+          render_maps: bool = False, ssim: bool = False, pointcloud: int = 0, pointcloud_crop=None, normals: bool = False):
     """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device, or a data.CameraRaysDataset (a
     photographed scene: the trainer makes its rays from the camera table, ``Trainer(ray_source=...)``).  ``render_maps``: the final
     test render also writes the depth / opacity maps of every image (``infer(maps=True)``).  ``ssim``: the periodic evaluation and
     the final test render also compute each image's SSIM (``evaluate(ssim=True)``; ``metrics_eval.json`` / ``metrics_test.json``).
     ``pointcloud`` > 0 (with `test_set` and `output`): after the final test render the test views' surface points, at most that
     many, go to ``pointcloud.ply`` (``points.export_pointcloud``; ``pointcloud_crop``: its ``crop``); with ``render_maps``
-    the maps of that render are used, so every view is rendered once.  At 0 nothing of it is imported, allocated or launched."""
+    the maps of that render are used, so every view is rendered once.  At 0 nothing of it is imported, allocated or launched.
+    ``normals`` (K-Planes and hash-grid methods; ``ValueError`` for the others, before the first step): the final test render also
+    writes normal maps (it implies ``render_maps``), and the point cloud carries normals (``points.export_oriented_pointcloud``)."""
     import json
+    if normals and cfg.method not in ("kplanes", "hashgrid"):
+        raise ValueError(f"train(normals=True): method {cfg.method!r} has no analytic density gradient (kplanes and hashgrid only)")
+    render_maps = render_maps or normals
     from dataclasses import asdict
     from .data import CameraRaysDataset
     on_cameras = isinstance(train_rays, CameraRaysDataset)
@@ -964,11 +978,13 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
     test_metrics = None
     if test_set is not None:
         idx = list(range(len(test_set)))
-        rendered = infer(tr, test_set, idx, output, "test_full", maps=render_maps)
+        rendered = infer(tr, test_set, idx, output, "test_full", maps=render_maps, normals=True) if normals else \
+            infer(tr, test_set, idx, output, "test_full", maps=render_maps)
         if pointcloud > 0 and output is not None:
-            from .points import export_pointcloud
-            export_pointcloud(tr, test_set, idx, output / "pointcloud.ply", n_points=pointcloud, crop=pointcloud_crop, seed=cfg.seed,
-                              rendered=rendered if render_maps else None)
+            from .points import export_oriented_pointcloud, export_pointcloud
+            (export_oriented_pointcloud if normals else export_pointcloud)(
+                tr, test_set, idx, output / "pointcloud.ply", n_points=pointcloud, crop=pointcloud_crop, seed=cfg.seed,
+                rendered=rendered if render_maps else None)
         if render_maps:
             rendered = [r["rgb"] for r in rendered]
         if test_set.rgbs:

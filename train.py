@@ -13,7 +13,7 @@ import uuid
 from pathlib import Path
 
 # (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight, --ssim,
-# --downscale, --holdout_every, --export_pointcloud and --pointcloud_crop
+# --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop and --normals
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -34,6 +34,8 @@ FLAGS = (
     ("--export_pointcloud", dict(type=int, default=0, metavar="N", help="write pointcloud.ply: at most N coloured surface points of the test views (0: off)")),
     ("--pointcloud_crop", dict(type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                                help="box the exported points must lie in (default: the box the marcher samples uniformly)")),
+    ("--normals", dict(action="store_true", help="kplanes / hashgrid: the final test render also writes normal maps (implies --render_maps) "
+                                                 "and pointcloud.ply carries normals")),
 )
 
 
@@ -41,7 +43,10 @@ def parse_args(argv=None):
     parser = argparse.ArgumentParser(prog="tinynerf", description="Train nerf (MI355X HIP path)")
     for flag, kw in FLAGS:
         parser.add_argument(flag, **kw)
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if args.normals and args.method not in ("kplanes", "hashgrid"):
+        parser.error(f"--normals needs --method kplanes or hashgrid: {args.method} has no analytic density gradient")
+    return args
 
 
 def fresh_run_dir(root: Path, args) -> Path:
@@ -97,7 +102,7 @@ def main(argv=None):
     cfg = TrainConfig(method=args.method, scene_type=args.scene_type, batch_size=args.batch_size, n_samples=args.n_samples, seed=seed,
                       distortion_weight=args.distortion_weight)
     train(cfg, train_rays, eval_set, test_set, run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim,
-          pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop)
+          pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop, normals=args.normals)
 
 
 if __name__ == "__main__":
