@@ -726,6 +726,51 @@ int tn_points_compact(const float *rays_o, const float *rays_d,                 
                       int32_t *src,                                             /* [capacity] ray index of each point */
                       int64_t *count,                                           /* device, 1 value */
                       void *workspace, void *stream);
+/* Triangle mesh of a scalar field on a regular grid: naive Surface Nets, all on the device.  fp32 throughout.
+ * Grid.  nx x ny x nz cells = dims[0..3) and (nx+1)(ny+1)(nz+1) nodes; node (i,j,k) sits at x_c = fmaf((float)idx_c, h_c, lo_c); dims,
+ *   lo[3] and h[3] are HOST arrays.  values holds one float per node, i fastest: index i + (nx+1)(j + (ny+1)k).  Cell (i,j,k) has the
+ *   linear index c = i + nx(j + ny k) and the corner nodes (i+dx, j+dy, k+dz).  A node is inside when value >= level (false for NaN).
+ *   The kernels are field-agnostic (the harness passes the logarithm of the density, level = log sigma).
+ * Vertices.  A cell is active when its 8 corners are neither all inside nor all outside.  Its 12 edges are taken in the order axis
+ *   a = 0, 1, 2 and within an axis the offsets (o_b, o_c) = (0,0), (1,0), (0,1), (1,1) on the axes b = (a+1)%3, c = (a+2)%3.  An edge
+ *   is crossed when its end nodes differ in insideness; its parameter is t = (level - v0) / (v1 - v0) -- two subtractions and a
+ *   correctly rounded division -- clamped to [0,1], v0 the end with 0 on axis a; t = 0.5 when either end value is not finite.  The
+ *   edge contributes the point (t on axis a, o_b on b, o_c on c).  u = (the contributions added in that order, starting from 0) /
+ *   (float)their number, per component; vertex p_c = fmaf((float)idx_c + u_c, h_c, lo_c).  The k-th active cell in cell order writes
+ *   vertex row k.  (Keep |values| <= 1e30: beyond, v1 - v0 overflows and t falls on an end of the edge.)
+ * Normal.  g_a = (sum over the 4 edges along a of (v1 - v0) w_b w_c) / h_a with w_b = u_b or 1 - u_b for o_b = 1 or 0, w_c likewise:
+ *   the gradient at u of the trilinear interpolant of the cell's own 8 corners.  n = -g / |g| when |g| > 0 and finite, else (0,0,0):
+ *   it points from inside (dense) to outside, as tn_kplanes_normals' does.
+ * Faces.  Cells in cell order, within a cell the axes a = 0, 1, 2: the edge from node (i,j,k) along a emits a quad when it is crossed
+ *   and idx_b >= 1 and idx_c >= 1, so that the 4 cells around it exist (all 4 are active).  Its corners q0..q3 are the vertex ids of
+ *   the cells at offsets (-1,-1), (0,-1), (0,0), (-1,0) on (b,c): counter-clockwise seen from +a; when the edge's lower node is
+ *   outside the order is reversed to (q3,q2,q1,q0).  The quad becomes the triangles (q0,q1,q2) and (q0,q2,q3): the m-th emitted quad
+ *   writes face rows 2m and 2m + 1 of 3 int32 each.  A surface that reaches the box is left open there.
+ * Counts.  counts[0] = vertices, counts[1] = triangles, whatever the capacities are; rows at or beyond a capacity are not written
+ *   and nothing at or beyond min(count, capacity) is touched; with a capacity of 0 that output may be NULL (both 0: counts only, two
+ *   launches).  normals may be NULL.  The ids in `faces` are those of the full mesh, whatever vertex_capacity is.
+ * tn_mesh_extract: four launches on `stream` (per-wave ballots + per-workgroup counts, one workgroup per count column scanning it,
+ *   ranked vertex stores + the cell -> vertex id map, ranked face stores), no atomics: the same bytes on every call.  `workspace`:
+ *   tn_mesh_workspace_bytes bytes, 8-byte aligned like `counts` (TN_E_ALIGN otherwise); with
+ *   G = ceil(cells / 256) it is G x 4 waves x 4 ballots of 8 B, then 2 x G workgroup counts of 8 B, then `cells` vertex ids of 4 B,
+ *   rounded up to 8 B: 144 G + 8 ceil(cells / 2).  After a call with a capacity > 0 the ids are every cell's vertex id in cell order,
+ *   -1 for a cell that is not active; the rest is undefined.  Checked before any launch: TN_E_NULL for null dims / lo / h, then TN_E_SIZE for a
+ *   negative dim or capacity or 2^31 cells or more (vertex ids are int32), TN_E_CONFIG for a level that is not finite, TN_E_NULL for
+ *   another null required pointer (values and the workspace are not read when a dim is 0: counts = 0, 0 and TN_OK), TN_E_ALIGN.
+ * tn_grid_nodes: the positions of nodes first .. first + n in node order, out[t] = node (first + t), by the fmaf above -- a field
+ *   sampled there is sampled at the very positions the vertices are built from.  One launch.  TN_E_SIZE unless the range lies inside
+ *   the grid's nodes.  No reference call site: the reference renders images and exports no geometry. */
+int tn_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int64_t *bytes);  /* host only */
+int tn_grid_nodes(const float *lo, const float *h, const int32_t *dims,         /* host arrays of 3 */
+                  int64_t first, int64_t n, float *out /* [n,3] */, void *stream);
+int tn_mesh_extract(const float *values,                                        /* [(nx+1)(ny+1)(nz+1)] device */
+                    const int32_t *dims, const float *lo, const float *h,       /* host arrays of 3 */
+                    float level, int64_t vertex_capacity, int64_t face_capacity,
+                    float *vertices,                                            /* [vertex_capacity,3] */
+                    float *normals,                                             /* [vertex_capacity,3] or NULL */
+                    int32_t *faces,                                             /* [face_capacity,3] */
+                    int64_t *counts,                                            /* device, 2 values */
+                    void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * optimizer step of the harness                       (reference run.py:186,258-260: torch.optim.Adam)

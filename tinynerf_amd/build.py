@@ -36,6 +36,7 @@ SOURCES = {
     "metrics.hip": FAST,
     "cameras.hip": FAST,
     "points.hip": FAST,
+    "mesh.hip": FAST,
     "kplanes.hip": FAST + ["-munsafe-fp-atomics"],
     "normals.hip": FAST,
     "cobafa.hip": STRICT + ["-munsafe-fp-atomics"],   # sawtooth warp x (res-1): an fma in f*x - floor moves taps

@@ -1,0 +1,247 @@
+"""Triangle mesh of a trained scene's density: the density sampled at the nodes of a regular grid over a box, its level
+set extracted by naive Surface Nets on the device -- one vertex per cell the surface passes through, one quad per grid edge it
+crosses; an indexed mesh, closed and consistently oriented wherever the surface does not reach the box --, written as a PLY.
+
+* ``extract`` -- ``tn_mesh_extract`` over a tensor of node values: vertices, normals, faces;
+* ``density_grid`` / ``extract_mesh`` -- the node values of a trainer / of any density callable, and their mesh;
+* ``export_mesh`` -- a trainer's mesh with vertex colours from its colour decoder, written to ``path``;
+* ``write_mesh_ply`` / ``read_mesh_ply`` -- binary little-endian PLY, 27 B per vertex, 13 B per face.
+
+The mesh is in the frame the rays are in: for a capture that is the frame after ``data.orient_poses``, not the capture's own.
+torch is plumbing only; there is no CPU path.  No reference counterpart: the reference renders images and exports no geometry.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Callable, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+MESH_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                        ("red", "u1"), ("green", "u1"), ("blue", "u1")])                       # packed: 27 B
+MESH_FACE = np.dtype([("n", "u1"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4")])                  # packed: 13 B
+_MESH_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                "property float nx\nproperty float ny\nproperty float nz\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+                "element face %d\nproperty list uchar int vertex_indices\nend_header\n")
+
+
+def _triple(x, ctype):
+    return (ctype * 3)(*[x[0], x[1], x[2]])
+
+
+def _grid(lo, h, dims):
+    """host arrays of the C ABI: lo / h as float32 (the values the kernels use), dims (nx, ny, nz)"""
+    lo32, h32 = np.asarray(lo, np.float32).reshape(3), np.asarray(h, np.float32).reshape(3)
+    return _triple(lo32.tolist(), C.c_float), _triple(h32.tolist(), C.c_float), _triple([int(d) for d in dims], C.c_int32)
+
+
+def grid_nodes(lo, h, dims: Sequence[int], first: int, n: int, device) -> torch.Tensor:
+    """``[n,3]`` world positions of nodes ``first .. first + n`` (x fastest) of the grid, ``fmaf(idx, h, lo)`` per axis (``tn_grid_nodes``)"""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("tinynerf_amd: grid_nodes needs a CUDA (HIP) device -- there is no CPU path")
+    out = torch.empty((int(n), 3), dtype=torch.float32, device=device)
+    lo_c, h_c, dims_c = _grid(lo, h, dims)
+    L.call("tn_grid_nodes", device, lo_c, h_c, dims_c, C.c_int64(first), C.c_int64(n), L.ptr(out))
+    return out
+
+
+def extract(values: torch.Tensor, lo, h, level: float, normals: bool = True, capacity: Optional[Tuple[int, int]] = None):
+    """``(vertices [V,3] float32, normals [V,3] float32 or None, faces [F,3] int32)`` on the device: the Surface Nets mesh of the level
+    set ``values == level`` (inside: ``values >= level``) of ``values [nz+1, ny+1, nx+1]``, the field at the nodes ``lo + idx h`` of a
+    grid of ``nx x ny x nz`` cells (include/tinynerf_hip.h has the definition).  The normals point from inside to outside.
+    ``capacity=None``: a count-only call, one read-back, then the call that writes; ``(vertex rows, face rows)``: one call into buffers
+    of that size -- at most that many rows come back (the first ones), the faces still naming the full mesh's vertices."""
+    if values.dim() != 3 or min(values.shape) < 1:
+        raise ValueError("extract: values must be [nz+1, ny+1, nx+1]")
+    v = values if values.dtype == torch.float32 and values.is_contiguous() else values.float().contiguous()
+    dev = L.require_cuda(v)
+    dims = (v.size(2) - 1, v.size(1) - 1, v.size(0) - 1)
+    lo_c, h_c, dims_c = _grid(lo, h, dims)
+    nbytes = C.c_int64(0)
+    L.call_plain("tn_mesh_workspace_bytes", dims_c[0], dims_c[1], dims_c[2], C.byref(nbytes))
+    workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+
+    def run(vcap: int, fcap: int):
+        vert = torch.empty((vcap, 3), dtype=torch.float32, device=dev)
+        nrm = torch.empty((vcap, 3), dtype=torch.float32, device=dev) if normals else None
+        faces = torch.empty((fcap, 3), dtype=torch.int32, device=dev)
+        L.call("tn_mesh_extract", dev, L.ptr(v), dims_c, lo_c, h_c, C.c_float(level), C.c_int64(vcap), C.c_int64(fcap),
+               L.ptr(vert) if vcap else None, L.ptr(nrm) if vcap else None, L.ptr(faces) if fcap else None, L.ptr(counts), L.ptr(workspace))
+        return vert, nrm, faces
+
+    if capacity is None:
+        run(0, 0)
+        n_v, n_f = counts.tolist()
+        return run(n_v, n_f)
+    vcap, fcap = int(capacity[0]), int(capacity[1])
+    if vcap < 0 or fcap < 0:
+        raise ValueError("extract: capacity must be >= 0")
+    vert, nrm, faces = run(vcap, fcap)
+    n_v, n_f = counts.tolist()
+    n_v, n_f = min(n_v, vcap), min(n_f, fcap)
+    return vert[:n_v], None if nrm is None else nrm[:n_v], faces[:n_f]
+
+
+def grid_dims(box, resolution: int):
+    """``(lo, h, dims)``: ``resolution`` cells on the longest axis of ``box`` (lo xyz, hi xyz), ``ceil(resolution extent / longest)``
+    on the others -- near-cubic cells; ``lo`` and ``h = extent / cells`` rounded to float32, as the kernels use them"""
+    box = np.asarray(box, np.float64).reshape(6)
+    extent = box[3:] - box[:3]
+    if int(resolution) < 1 or not (extent > 0).all() or not np.isfinite(box).all():
+        raise ValueError("mesh: resolution must be >= 1 and the box finite with a positive extent on every axis")
+    dims = [max(1, int(math.ceil(int(resolution) * e / extent.max() - 1e-9))) for e in extent]
+    lo = box[:3].astype(np.float32)
+    return lo, (extent / np.float64(dims)).astype(np.float32), tuple(dims)
+
+
+@torch.no_grad()
+def _log_density(sigma_fn: Callable, contraction, lo, h, dims, device, chunk: int) -> torch.Tensor:
+    nx, ny, nz = dims
+    n = (nx + 1) * (ny + 1) * (nz + 1)
+    out = torch.empty(n, dtype=torch.float32, device=device)
+    for first in range(0, n, chunk):
+        m = min(chunk, n - first)
+        x = grid_nodes(lo, h, dims, first, m, device)
+        if contraction is not None:
+            x = contraction(x)[0]                          # exactly as the sampler contracts a sample
+        sigma = sigma_fn(x).detach().reshape(-1).float()
+        out[first:first + m] = torch.log(sigma.clamp_min(1e-30))
+    return out.view(nz + 1, ny + 1, nx + 1)
+
+
+def density_grid(trainer, box, dims: Sequence[int], chunk: int = 1 << 21):
+    """``(values [nz+1, ny+1, nx+1], lo, h)``: ``log(max(sigma, 1e-30))`` of the trainer's density at the nodes of ``box`` (lo xyz, hi xyz)
+    cut into ``dims = (nx, ny, nz)`` cells -- the nodes from ``tn_grid_nodes``, contracted with the trainer's contraction,
+    ``trainer.sigma_fn`` under ``no_grad``, ``chunk`` nodes per call"""
+    box = np.asarray(box, np.float64).reshape(6)
+    dims = tuple(int(d) for d in dims)
+    lo, h = box[:3].astype(np.float32), ((box[3:] - box[:3]) / np.float64(dims)).astype(np.float32)
+    trainer.renderer.eval()
+    return _log_density(trainer.sigma_fn, trainer.ray_provider.contraction, lo, h, dims, trainer.device, chunk), lo, h
+
+
+def default_level(h) -> float:
+    """the density at which a segment one cell long has opacity 0.5 -- ``compact_points``' ``min_opacity``: ``ln 2 / max(h)``"""
+    return math.log(2.0) / float(np.max(np.asarray(h, np.float64)))
+
+
+def extract_mesh(sigma_fn: Callable, box, resolution: int, level: Optional[float] = None, contraction=None, device=None,
+                 chunk: int = 1 << 21):
+    """``extract`` of ``log sigma_fn`` on the grid ``grid_dims(box, resolution)``, for any callable from points ``[n,3]`` on the device
+    (contracted by ``contraction`` first, when given) to densities ``[n]``.  ``level``: the density of the surface (default
+    ``default_level``).  Returns ``(vertices, normals, faces)``."""
+    lo, h, dims = grid_dims(box, resolution)
+    device = torch.device("cuda") if device is None else device
+    values = _log_density(sigma_fn, contraction, lo, h, dims, device, chunk)
+    sigma = default_level(h) if level is None else float(level)
+    if not sigma > 0.0 or not math.isfinite(sigma):
+        raise ValueError("mesh: level is a density: it must be finite and > 0")
+    return extract(values, lo, h, math.log(sigma))
+
+
+def color_bytes(c: torch.Tensor) -> torch.Tensor:
+    """colours -> bytes as ``tn_points_compact`` does: clamp to [0,1] with NaN -> 0, ``(uint8) fmaf(c, 255, 0.5)`` (the float64 product
+    and sum are exact: their rounding to float32 is the fma's)"""
+    c = c.float()
+    c = torch.where(c > 0, c.clamp_max(1.0), torch.zeros_like(c))
+    return (c.double() * 255.0 + 0.5).float().to(torch.uint8)
+
+
+@torch.no_grad()
+def vertex_colors(trainer, vertices: torch.Tensor, normals: torch.Tensor, chunk: int = 1 << 20) -> torch.Tensor:
+    """``[V,3] uint8``: the colour decoder's output at the vertices -- the feature module at the contracted vertex, the view direction
+    ``-n`` (looking at the surface head-on), ``(0,0,-1)`` where ``n = 0``"""
+    r = trainer.renderer
+    r.eval()
+    out = torch.empty((vertices.size(0), 3), dtype=torch.uint8, device=vertices.device)
+    for k in range(0, vertices.size(0), chunk):
+        x, n = vertices[k:k + chunk], normals[k:k + chunk]
+        d = torch.where((n == 0).all(1, keepdim=True), torch.tensor([0.0, 0.0, -1.0], device=n.device), -n).contiguous()
+        feats = r.feature_module(trainer.ray_provider.contraction(x.contiguous())[0])
+        out[k:k + chunk] = color_bytes(r.rgb_decoder(feats, d))
+    return out
+
+
+@torch.no_grad()
+def export_mesh(trainer, path=None, resolution: int = 256, level: Optional[float] = None, crop=None, colors: bool = True):
+    """The mesh of the trainer's density inside ``crop`` (6 values, lo xyz then hi xyz; ``None``: ``points.default_crop`` of its
+    configuration) on ``grid_dims(crop, resolution)``, at the density ``level`` (default ``default_level``).  Returns ``(vertices [V,3]
+    float32, normals [V,3] float32, colors [V,3] uint8, faces [F,3] int32)`` on the device -- ``colors`` (``vertex_colors``) zeros
+    when switched off -- and writes ``path`` (``write_mesh_ply``) when one is given."""
+    if getattr(trainer, "world", 1) > 1:
+        raise ValueError("export_mesh runs on one rank: world_size > 1 is not supported")
+    from .points import default_crop
+    lo, h, dims = grid_dims(default_crop(trainer.cfg) if crop is None else crop, resolution)
+    sigma = default_level(h) if level is None else float(level)
+    if not sigma > 0.0 or not math.isfinite(sigma):
+        raise ValueError("export_mesh: level is a density: it must be finite and > 0")
+    trainer.renderer.eval()
+    values = _log_density(trainer.sigma_fn, trainer.ray_provider.contraction, lo, h, dims, trainer.device, 1 << 21)
+    vertices, normals, faces = extract(values, lo, h, math.log(sigma))
+    rgb = vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=vertices.device)
+    if path is not None:
+        write_mesh_ply(path, vertices, normals, rgb, faces)
+    return vertices, normals, rgb, faces
+
+
+def _host(x, dtype) -> np.ndarray:
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    return np.ascontiguousarray(x, dtype=dtype)
+
+
+def write_mesh_ply(path, vertices, normals, colors, faces) -> None:
+    """Binary little-endian PLY 1.0: ``element vertex V`` with float x y z, float nx ny nz, uchar red green blue (27 B each), then
+    ``element face F`` with ``property list uchar int vertex_indices`` (a 3 and three int32: 13 B each).  Tensors or arrays."""
+    xyz, nrm = _host(vertices, np.float32).reshape(-1, 3), _host(normals, np.float32).reshape(-1, 3)
+    rgb, tri = _host(colors, np.uint8).reshape(-1, 3), _host(faces, np.int32).reshape(-1, 3)
+    if not (xyz.shape[0] == nrm.shape[0] == rgb.shape[0]):
+        raise ValueError("write_mesh_ply: vertices, normals and colors differ in length")
+    vertex = np.empty(xyz.shape[0], dtype=MESH_VERTEX)
+    for k, name in enumerate(("x", "y", "z")):
+        vertex[name] = xyz[:, k]
+    for k, name in enumerate(("nx", "ny", "nz")):
+        vertex[name] = nrm[:, k]
+    for k, name in enumerate(("red", "green", "blue")):
+        vertex[name] = rgb[:, k]
+    face = np.empty(tri.shape[0], dtype=MESH_FACE)
+    face["n"] = 3
+    for k, name in enumerate(("a", "b", "c")):
+        face[name] = tri[:, k]
+    with open(path, "wb") as f:
+        f.write((_MESH_HEADER % (vertex.shape[0], face.shape[0])).encode("ascii"))
+        f.write(vertex.tobytes())
+        f.write(face.tobytes())
+
+
+def read_mesh_ply(path):
+    """``(vertices [V,3] float32, normals [V,3] float32, colors [V,3] uint8, faces [F,3] int32)`` as numpy arrays from a file in
+    ``write_mesh_ply``'s dialect; any other header, a body of another length or a face that is not a triangle raises ``ValueError``"""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"{path}: not a PLY file (no end_header)")
+    head, body = raw[:end + 11].decode("ascii", errors="replace"), raw[end + 11:]
+    lines = head.split("\n")
+    try:
+        n_v = int(lines[2].split()[2]) if lines[2].startswith("element vertex ") else -1
+        n_f = int(lines[12].split()[2]) if lines[12].startswith("element face ") else -1
+    except (IndexError, ValueError):
+        n_v = n_f = -1
+    if n_v < 0 or n_f < 0 or head != _MESH_HEADER % (n_v, n_f):
+        raise ValueError(f"{path}: not the mesh PLY dialect (binary little-endian, float xyz + float normals + uchar rgb, triangle list)")
+    if len(body) != MESH_VERTEX.itemsize * n_v + MESH_FACE.itemsize * n_f:
+        raise ValueError(f"{path}: {len(body)} bytes of elements, the header promises {MESH_VERTEX.itemsize * n_v + MESH_FACE.itemsize * n_f}")
+    vertex = np.frombuffer(body, dtype=MESH_VERTEX, count=n_v)
+    face = np.frombuffer(body, dtype=MESH_FACE, count=n_f, offset=MESH_VERTEX.itemsize * n_v)
+    if n_f and not (face["n"] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    return (np.stack([vertex["x"], vertex["y"], vertex["z"]], 1), np.stack([vertex["nx"], vertex["ny"], vertex["nz"]], 1),
+            np.stack([vertex["red"], vertex["green"], vertex["blue"]], 1), np.stack([face["a"], face["b"], face["c"]], 1))

@@ -13,7 +13,7 @@ import uuid
 from pathlib import Path
 
 # (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight, --ssim,
-# --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop and --normals
+# --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop, --normals, --export_mesh, --mesh_level and --mesh_crop
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -36,6 +36,10 @@ FLAGS = (
                                help="box the exported points must lie in (default: the box the marcher samples uniformly)")),
     ("--normals", dict(action="store_true", help="kplanes / hashgrid: the final test render also writes normal maps (implies --render_maps) "
                                                  "and pointcloud.ply carries normals")),
+    ("--export_mesh", dict(type=int, default=0, metavar="R", help="write mesh.ply: the density's surface as a triangle mesh, R cells on the longest axis of the box (0: off)")),
+    ("--mesh_level", dict(type=float, default=None, metavar="SIGMA", help="density of the exported surface (default: ln 2 / cell size, opacity 0.5 across a cell)")),
+    ("--mesh_crop", dict(type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
+                         help="box the mesh is extracted in (default: the box the marcher samples uniformly)")),
 )
 
 
@@ -102,7 +106,8 @@ def main(argv=None):
     cfg = TrainConfig(method=args.method, scene_type=args.scene_type, batch_size=args.batch_size, n_samples=args.n_samples, seed=seed,
                       distortion_weight=args.distortion_weight)
     train(cfg, train_rays, eval_set, test_set, run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim,
-          pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop, normals=args.normals)
+          pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop, normals=args.normals,
+          mesh=args.export_mesh, mesh_level=args.mesh_level, mesh_crop=args.mesh_crop)
 
 
 if __name__ == "__main__":
