@@ -771,6 +771,57 @@ int tn_mesh_extract(const float *values,                                        
                     int32_t *faces,                                             /* [face_capacity,3] */
                     int64_t *counts,                                            /* device, 2 values */
                     void *workspace, void *stream);
+/* Connected components of an indexed triangle mesh, and the filter that keeps the large ones: all on the device, integers throughout.
+ * Input.  V vertices and F faces, faces [F,3] int32.  A face is valid when its three indices lie in [0, V); an invalid face takes no
+ *   part in anything and is always dropped (tn_mesh_extract with a vertex_capacity below its vertex count hands back fewer vertex rows
+ *   than its faces name).  A valid face with repeated indices is an ordinary face.
+ * Components.  Two vertices are connected when a valid face names both; label[v] is the smallest vertex id of v's component (the
+ *   transitive closure); a vertex in no valid face is its own component, label[v] = v.
+ * Face counts.  face_count[r] = the number of valid faces whose vertices carry label r -- 0 for every v with label[v] != v.
+ *   stats[0] = the number of components (label[v] == v), stats[1] = those with at least one face, stats[2] = the largest face_count.
+ * Filter, with a threshold T >= 0.  Vertex v is kept when face_count[label[v]] >= T; a valid face is kept when its component is.
+ *   Kept vertices keep their order: the k-th kept vertex becomes row k of out_vertices / out_normals / out_colors -- its rows copied bit
+ *   for bit -- and src[k] is its old id.  Kept faces keep their order, their indices renumbered to the new rows.  normals and colors
+ *   (uint8 [V,3]) may be NULL; their outputs are then not written.  counts[0] = kept vertices, counts[1] = kept faces, whatever the
+ *   capacities are; rows at or beyond a capacity are not written and nothing at or beyond min(count, capacity) is touched; with a
+ *   capacity of 0 that side's outputs may be NULL (both 0: counts only, two launches).  The indices in out_faces are those of the whole
+ *   filtered mesh, whatever vertex_capacity is.  T = 0 on a mesh with only valid faces is the identity.  labels and face_counts are
+ *   tn_mesh_components' outputs for the same faces (a label outside [0, V) drops its vertex).
+ * tn_mesh_components: six launches on `stream`, no host read-back and no loop driven from the host -- labels[v] = v and face_counts = 0;
+ *   one pass over the faces, a lock-free union-find on `labels` itself (the larger of two roots is linked under the smaller with
+ *   atomicCAS, retried after a lost race, paths shortened with atomicMin on the way up); one pass that makes every labels[v] its
+ *   root; integer atomicAdd of the valid faces into face_counts[label], one add per label and wave; per-workgroup partial stats;
+ *   one workgroup reducing them in a fixed order.  These atomics choose the route, not the result: the smaller id always wins, so
+ *   the final root is the component's minimum whatever the interleaving, and integer min and integer sum do not depend on the order
+ *   of their operands -- the same bytes on every call, as for the entry points above that use no atomics.  `workspace`:
+ *   tn_mesh_components_workspace_bytes = 24 ceil(V / 256) bytes, 8-byte aligned like `stats`; contents undefined afterwards.
+ * tn_mesh_filter: four launches, no atomics (per-wave ballots of kept vertices and faces + per-workgroup counts, one workgroup per
+ *   count column scanning it, ranked vertex stores + the old -> new map, ranked face stores through the map).  `workspace`:
+ *   tn_mesh_filter_workspace_bytes; with G = ceil(max(V, F) / 256) it is G x 4 waves x 2 ballots of 8 B, then 2 x G workgroup counts of
+ *   8 B, then V new ids of 4 B (-1: dropped) rounded up to 8 B: 80 G + 8 ceil(V / 2); 8-byte aligned like `counts`.
+ * Checked before any launch, for both: TN_E_SIZE for a negative size or capacity or V or F >= 2^31 (ids are int32); TN_E_CONFIG for
+ *   threshold < 0; TN_E_NULL for a null required pointer (stats / counts always; with V > 0 labels, face_counts and the workspace,
+ *   faces with F > 0; with vertex_capacity > 0 vertices, out_vertices, src and the output of every attribute that is given; with
+ *   face_capacity > 0 out_faces); TN_E_ALIGN.  F == 0 gives every vertex its own component.  V == 0 writes stats / counts of 0 and
+ *   returns TN_OK: the inputs and the workspace are not read.  No reference call site: the reference exports no geometry. */
+int tn_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t *bytes);   /* host only */
+int tn_mesh_components(const int32_t *faces,                                    /* [n_faces,3] device */
+                       int64_t n_vertices, int64_t n_faces,
+                       int32_t *labels,                                         /* [n_vertices] */
+                       int32_t *face_counts,                                    /* [n_vertices] */
+                       int64_t *stats,                                          /* device, 3 values */
+                       void *workspace, void *stream);
+int tn_mesh_filter_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t *bytes);       /* host only */
+int tn_mesh_filter(const int32_t *faces, const int32_t *labels, const int32_t *face_counts, int64_t threshold,
+                   const float *vertices,                                       /* [n_vertices,3] */
+                   const float *normals,                                        /* [n_vertices,3] or NULL */
+                   const uint8_t *colors,                                       /* [n_vertices,3] or NULL */
+                   int64_t n_vertices, int64_t n_faces, int64_t vertex_capacity, int64_t face_capacity,
+                   float *out_vertices, float *out_normals, uint8_t *out_colors,  /* [vertex_capacity,3] each */
+                   int32_t *src,                                                /* [vertex_capacity] old id of each kept vertex */
+                   int32_t *out_faces,                                          /* [face_capacity,3] */
+                   int64_t *counts,                                             /* device, 2 values */
+                   void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * optimizer step of the harness                       (reference run.py:186,258-260: torch.optim.Adam)

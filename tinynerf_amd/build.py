@@ -50,6 +50,7 @@ SOURCES = {
     "mlp_f2_layers.hip": FAST + ["-munsafe-fp-atomics"],
     "mlp_fused_f2.hip": FAST,
     "mlp_b3_layers.hip": FAST + ["-munsafe-fp-atomics"],
+    "mesh_components.hip": FAST,      # mesh.hip's flags; last, so that the objects before it link where they did
 }
 
 

@@ -190,6 +190,105 @@ def export_mesh(trainer, path=None, resolution: int = 256, level: Optional[float
     return vertices, normals, rgb, faces
 
 
+def components(faces: torch.Tensor, n_vertices: int):
+    """``(labels [V] int32, face_counts [V] int32, stats)`` of the mesh ``faces [F,3] int32`` over ``n_vertices`` vertices
+    (``tn_mesh_components``): ``labels[v]`` the smallest vertex id of ``v``'s connected component, ``face_counts[r]`` the
+    valid faces of the component whose label is ``r`` (0 elsewhere), ``stats = (components, components with a face, largest face
+    count)`` as ints, from one read-back.  A face with an index outside ``[0, n_vertices)`` takes no part."""
+    V = int(n_vertices)
+    if faces.dim() != 2 or faces.size(1) != 3 or faces.dtype != torch.int32 or V < 0:
+        raise ValueError("components: faces must be [F,3] int32 and n_vertices >= 0")
+    dev = L.require_cuda(faces)
+    F = faces.size(0)
+    nbytes = C.c_int64(0)
+    L.call_plain("tn_mesh_components_workspace_bytes", C.c_int64(V), C.c_int64(F), C.byref(nbytes))
+    workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    labels, face_counts = torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev)
+    stats = torch.empty(3, dtype=torch.int64, device=dev)
+    L.call("tn_mesh_components", dev, L.ptr(faces) if F else None, C.c_int64(V), C.c_int64(F), L.ptr(labels) if V else None,
+           L.ptr(face_counts) if V else None, L.ptr(stats), L.ptr(workspace) if V else None)
+    return labels, face_counts, tuple(stats.tolist())
+
+
+def component_threshold(min_faces: int, keep_fraction: float, largest: int) -> int:
+    """The filter's face-count threshold ``T = max(min_faces, ceil(keep_fraction * largest))``, in exact arithmetic (the float
+    ``keep_fraction`` taken as the rational it is): ``keep_fraction = 1.0`` gives ``largest`` -- only the largest component stays,
+    ties all kept.  ``ValueError`` for ``min_faces < 0``, for ``keep_fraction`` outside ``[0, 1]`` or NaN."""
+    from fractions import Fraction
+    if isinstance(min_faces, bool) or int(min_faces) != min_faces or int(min_faces) < 0:
+        raise ValueError("filter_components: min_faces must be an integer >= 0")
+    k = float(keep_fraction)
+    if not 0.0 <= k <= 1.0:                                        # (NaN fails both comparisons)
+        raise ValueError("filter_components: keep_fraction must lie in [0, 1]")
+    return max(int(min_faces), math.ceil(Fraction(k) * int(largest)))
+
+
+def filter_components(vertices: torch.Tensor, normals: Optional[torch.Tensor], colors: Optional[torch.Tensor], faces: torch.Tensor,
+                      min_faces: int = 0, keep_fraction: float = 0.0, return_src: bool = False):
+    """``(vertices, normals, colors, faces)`` on the device -- and ``src [V'] int32``, the old id of every kept vertex, with
+    ``return_src`` --: the connected components of the mesh with at least ``component_threshold(min_faces, keep_fraction, largest)``
+    faces (``tn_mesh_components`` + ``tn_mesh_filter``).  Kept vertices and faces keep their order, the rows are copied bit
+    for bit, the faces renumbered; faces with an index outside ``[0, V)`` are dropped.  ``normals`` / ``colors`` (``[V,3] uint8``) may
+    be ``None`` and come back as ``None``.  One read-back for the statistics, a count-only call, one read-back, the writing call."""
+    component_threshold(min_faces, keep_fraction, 0)               # the arguments, before any device work
+    if vertices.dim() != 2 or vertices.size(1) != 3 or vertices.dtype != torch.float32 or faces.dtype != torch.int32:
+        raise ValueError("filter_components: vertices must be [V,3] float32 and faces [F,3] int32")
+    V, F = vertices.size(0), faces.size(0)
+    for name, t, dtype in (("normals", normals, torch.float32), ("colors", colors, torch.uint8)):
+        if t is not None and (t.shape != vertices.shape or t.dtype != dtype):
+            raise ValueError(f"filter_components: {name} must be [V,3] {dtype}")
+    dev = L.require_cuda(vertices, normals, colors, faces)
+    labels, face_counts, stats = components(faces, V)
+    threshold = component_threshold(min_faces, keep_fraction, stats[2])
+    nbytes = C.c_int64(0)
+    L.call_plain("tn_mesh_filter_workspace_bytes", C.c_int64(V), C.c_int64(F), C.byref(nbytes))
+    workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+
+    def run(vcap: int, fcap: int):
+        out_v = torch.empty((vcap, 3), dtype=torch.float32, device=dev)
+        out_n = None if normals is None else torch.empty((vcap, 3), dtype=torch.float32, device=dev)
+        out_c = None if colors is None else torch.empty((vcap, 3), dtype=torch.uint8, device=dev)
+        src = torch.empty(vcap, dtype=torch.int32, device=dev)
+        out_f = torch.empty((fcap, 3), dtype=torch.int32, device=dev)
+        some = lambda t, n: L.ptr(t) if n and t is not None else None      # noqa: E731  (an empty tensor's pointer is not passed)
+        L.call("tn_mesh_filter", dev, some(faces, F), some(labels, V), some(face_counts, V), C.c_int64(threshold), some(vertices, V),
+               some(normals, V), some(colors, V), C.c_int64(V), C.c_int64(F), C.c_int64(vcap), C.c_int64(fcap), some(out_v, vcap),
+               some(out_n, vcap), some(out_c, vcap), some(src, vcap), some(out_f, fcap), L.ptr(counts), some(workspace, V))
+        return out_v, out_n, out_c, out_f, src
+
+    run(0, 0)
+    n_v, n_f = counts.tolist()
+    out = run(n_v, n_f)
+    return out if return_src else out[:4]
+
+
+@torch.no_grad()
+def export_clean_mesh(trainer, path=None, resolution: int = 256, level: Optional[float] = None, crop=None, colors: bool = True,
+                      min_faces: int = 0, keep_fraction: float = 0.0):
+    """``export_mesh`` with ``filter_components(min_faces, keep_fraction)`` between the extraction and the colours: floaters and
+    fragments below the threshold leave the mesh, and the colour decoder is only asked about vertices that stay.  With both options
+    at 0 it returns and writes exactly what ``export_mesh`` does."""
+    if getattr(trainer, "world", 1) > 1:
+        raise ValueError("export_clean_mesh runs on one rank: world_size > 1 is not supported")
+    component_threshold(min_faces, keep_fraction, 0)
+    if not min_faces and not keep_fraction:
+        return export_mesh(trainer, path, resolution=resolution, level=level, crop=crop, colors=colors)
+    from .points import default_crop
+    lo, h, dims = grid_dims(default_crop(trainer.cfg) if crop is None else crop, resolution)
+    sigma = default_level(h) if level is None else float(level)
+    if not sigma > 0.0 or not math.isfinite(sigma):
+        raise ValueError("export_clean_mesh: level is a density: it must be finite and > 0")
+    trainer.renderer.eval()
+    values = _log_density(trainer.sigma_fn, trainer.ray_provider.contraction, lo, h, dims, trainer.device, 1 << 21)
+    vertices, normals, faces = extract(values, lo, h, math.log(sigma))
+    vertices, normals, _, faces = filter_components(vertices, normals, None, faces, min_faces=min_faces, keep_fraction=keep_fraction)
+    rgb = vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=vertices.device)
+    if path is not None:
+        write_mesh_ply(path, vertices, normals, rgb, faces)
+    return vertices, normals, rgb, faces
+
+
 def _host(x, dtype) -> np.ndarray:
     if isinstance(x, torch.Tensor):
         x = x.detach().cpu().numpy()

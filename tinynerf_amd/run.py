@@ -937,7 +937,8 @@ def evaluate(dataset, rendered: List[torch.Tensor], indices: List[int], ssim: bo
 def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=None, eval_every: Optional[int] = None,
           eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
           render_maps: bool = False, ssim: bool = False, pointcloud: int = 0, pointcloud_crop=None,
-          mesh: int = 0, mesh_level: Optional[float] = None, mesh_crop=None, normals: bool = False):
+          mesh: int = 0, mesh_level: Optional[float] = None, mesh_crop=None, mesh_min_faces: int = 0, mesh_keep_fraction: float = 0.0,
+          normals: bool = False):
     """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device, or a data.CameraRaysDataset (a
     photographed scene: the trainer makes its rays from the camera table, ``Trainer(ray_source=...)``).  ``render_maps``: the final
     test render also writes the depth / opacity maps of every image (``infer(maps=True)``).  ``ssim``: the periodic evaluation and
@@ -949,7 +950,9 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
     writes normal maps (it implies ``render_maps``), and the point cloud carries normals (``points.export_oriented_pointcloud``).
     ``mesh`` > 0 (with `test_set` and `output`): after the final test render the density's surface goes to ``mesh.ply``, ``mesh`` cells
     on the longest axis of the box (``mesh.export_mesh``; ``mesh_level``, ``mesh_crop``: its ``level`` and ``crop``).  At 0
-    nothing of it is imported, allocated or launched."""
+    nothing of it is imported, allocated or launched.  ``mesh_min_faces`` / ``mesh_keep_fraction``: when one of them is not 0 the mesh
+    goes through ``mesh.export_clean_mesh`` instead -- only the connected components with at least ``max(mesh_min_faces,
+    ceil(mesh_keep_fraction x the largest component's faces))`` faces are written; with both 0 ``export_mesh`` is called as before."""
     import json
     if normals and cfg.method not in ("kplanes", "hashgrid"):
         raise ValueError(f"train(normals=True): method {cfg.method!r} has no analytic density gradient (kplanes and hashgrid only)")
@@ -990,8 +993,13 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
                 tr, test_set, idx, output / "pointcloud.ply", n_points=pointcloud, crop=pointcloud_crop, seed=cfg.seed,
                 rendered=rendered if render_maps else None)
         if mesh > 0 and output is not None:
-            from .mesh import export_mesh
-            export_mesh(tr, output / "mesh.ply", resolution=mesh, level=mesh_level, crop=mesh_crop)
+            if mesh_min_faces or mesh_keep_fraction:
+                from .mesh import export_clean_mesh
+                export_clean_mesh(tr, output / "mesh.ply", resolution=mesh, level=mesh_level, crop=mesh_crop, min_faces=mesh_min_faces,
+                                  keep_fraction=mesh_keep_fraction)
+            else:
+                from .mesh import export_mesh
+                export_mesh(tr, output / "mesh.ply", resolution=mesh, level=mesh_level, crop=mesh_crop)
         if render_maps:
             rendered = [r["rgb"] for r in rendered]
         if test_set.rgbs:

@@ -13,7 +13,7 @@ import uuid
 from pathlib import Path
 
 # (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight, --ssim,
-# --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop, --normals, --export_mesh, --mesh_level and --mesh_crop
+# --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop, --normals, --export_mesh, --mesh_level, --mesh_crop, --mesh_min_faces and --mesh_keep_fraction
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -40,6 +40,9 @@ FLAGS = (
     ("--mesh_level", dict(type=float, default=None, metavar="SIGMA", help="density of the exported surface (default: ln 2 / cell size, opacity 0.5 across a cell)")),
     ("--mesh_crop", dict(type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"),
                          help="box the mesh is extracted in (default: the box the marcher samples uniformly)")),
+    ("--mesh_min_faces", dict(type=int, default=0, metavar="N", help="with --export_mesh: drop the connected pieces of the mesh with fewer than N triangles (0: keep all)")),
+    ("--mesh_keep_fraction", dict(type=float, default=0.0, metavar="F", help="with --export_mesh: drop the pieces with fewer than F x the largest piece's triangles "
+                                                                               "(1.0: the largest piece alone; 0: keep all)")),
 )
 
 
@@ -50,6 +53,10 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.normals and args.method not in ("kplanes", "hashgrid"):
         parser.error(f"--normals needs --method kplanes or hashgrid: {args.method} has no analytic density gradient")
+    if (args.mesh_min_faces or args.mesh_keep_fraction) and not args.export_mesh:
+        parser.error("--mesh_min_faces and --mesh_keep_fraction filter the mesh of --export_mesh R: give that too")
+    if args.mesh_min_faces < 0 or not 0.0 <= args.mesh_keep_fraction <= 1.0:
+        parser.error("--mesh_min_faces must be >= 0 and --mesh_keep_fraction lie in [0, 1]")
     return args
 
 
@@ -107,7 +114,8 @@ def main(argv=None):
                       distortion_weight=args.distortion_weight)
     train(cfg, train_rays, eval_set, test_set, run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim,
           pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop, normals=args.normals,
-          mesh=args.export_mesh, mesh_level=args.mesh_level, mesh_crop=args.mesh_crop)
+          mesh=args.export_mesh, mesh_level=args.mesh_level, mesh_crop=args.mesh_crop, mesh_min_faces=args.mesh_min_faces,
+          mesh_keep_fraction=args.mesh_keep_fraction)
 
 
 if __name__ == "__main__":
