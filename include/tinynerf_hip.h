@@ -822,9 +822,71 @@ int tn_mesh_filter(const int32_t *faces, const int32_t *labels, const int32_t *f
                    int32_t *out_faces,                                          /* [face_capacity,3] */
                    int64_t *counts,                                             /* device, 2 values */
                    void *workspace, void *stream);
+/* Fusion of depth maps into a truncated signed distance field (TSDF) on tn_mesh_extract's grid, and the mask that keeps the extractor's
+ * faces out of cells no view has observed: all on the device, fp32 throughout, every fused multiply-add an explicit fmaf.
+ * Grid.  Exactly tn_mesh_extract's: nx x ny x nz cells = dims[0..3), node (i,j,k) at x_c = fmaf((float)idx_c, h_c, lo_c), nodes stored
+ *   i fastest: index i + (nx+1)(j + (ny+1)k); dims, lo[3] and h[3] are HOST arrays.
+ * State.  Two floats per node: S, the sum of truncated normalised distances, and W, the number of contributions.  The caller zeroes
+ *   both before the first call; every call adds to them.
+ * Inputs.  A tn_camera_table (its rgb is not read); depth [n_pixels], a distance along the unit ray as tn_ray_maps and
+ *   tn_points_compact use it, in the table's flat pixel order; opacity [n_pixels] or NULL, with min_opacity; trunc > 0; the views
+ *   view_first .. view_first + view_count of the table.
+ * Update of node x, for the views of the range in ASCENDING order -- "skip" means this view adds nothing:
+ *   1 camera frame: p = x - t (t the translation column), q = R^T p, z = -q_z (OpenGL axes: the camera looks down -z); skip unless
+ *     z > 0; x' = q_x / z, y' = -q_y / z (image axes, y down); the sums are fmaf(R0c, p_0, fmaf(R1c, p_1, R2c * p_2)), the divisions
+ *     correctly rounded
+ *   2 lens, the forward model of tn_camera_rays' lenses, r^2 = fmaf(x', x', y' * y'), polynomials by Horner's rule in fmaf:
+ *     model 0 (pinhole): (xd, yd) = (x', y')
+ *     model 1 (OpenCV):  xd = x' rad + 2 p1 x' y' + p2 (r^2 + 2 x'^2), yd = y' rad + 2 p2 x' y' + p1 (r^2 + 2 y'^2),
+ *                        rad = 1 + k1 r^2 + k2 r^4 + k3 r^6 + k4 r^8
+ *     model 2 (fisheye): theta = atan(r), theta_d = theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8),
+ *                        (xd, yd) = (x', y') theta_d / r, and (x', y') itself at r = 0
+ *   3 monotonicity guard (models 1 and 2): skip unless 1 + 3 k1 s + 5 k2 s^2 + 7 k3 s^3 + 9 k4 s^4 > 0, s = r^2 for OpenCV and
+ *     theta^2 for the fisheye -- where the radial map has turned back the forward model folds far-off points into the image.  LIMIT:
+ *     the guard is local.  It looks at the slope at the point itself: a point beyond a fold where the slope is positive again, and a
+ *     fold that the tangential terms make, pass it.
+ *   4 pixel: u = fmaf(fx, xd, cx), v = fmaf(fy, yd, cy); pixel i covers [i, i + 1) (centres at +0.5, as in tn_camera_rays): skip
+ *     unless 0 <= u < w and 0 <= v < h (false for NaN); g = pixel_offset[view] + floor(v) w + floor(u)
+ *   5 depth gate: skip unless D = depth[g] is finite and > 0 and -- with opacity -- opacity[g] >= min_opacity (false for NaN)
+ *   6 sdf = D - |p|, |p| = sqrt(fmaf(p_0, p_0, fmaf(p_1, p_1, p_2 * p_2))); skip when sdf < -trunc (the node is hidden behind the
+ *     surface in this view); otherwise S += min(sdf / trunc, 1) (a correctly rounded division) and W += 1: free space in front of the
+ *     surface votes +1.
+ *   The result depends on the inputs alone: no atomics, one lane owns a node, and a range of views integrated in one call gives the
+ *   same bytes as the same range split over several calls in order -- the host may feed the views in chunks of any size.
+ * Mesh field (host): values = -S / W where W > 0, -1 (empty) elsewhere; level 0; inside is value >= 0.
+ * tn_tsdf_integrate: one launch on `stream`, one lane per node, 256 per workgroup, the loop over the views inside the kernel; a
+ *   view's table row is read with wave-uniform (scalar) loads.  Checked before the launch: TN_E_NULL for null cams / dims / lo / h,
+ *   then TN_E_SIZE for a negative dim or count, a view range outside the table or 2^31 nodes or more; TN_E_CONFIG for a trunc that is
+ *   not finite or <= 0; TN_E_NULL for another null required pointer (opacity is optional); TN_E_ALIGN (4 bytes).  view_count == 0 or
+ *   a dim of 0: TN_OK without a launch, S and W untouched.
+ * tn_tsdf_mask_faces: a cell with any corner at W == 0 must produce no geometry -- otherwise every surface gets a second sheet,
+ *   trunc behind it, where the field falls from inside to "empty".  cell_ids [cells] is tn_mesh_extract's cell -> vertex id map (its
+ *   workspace from byte 144 G on, after a writing call; -1: no vertex), n_vertices its V, faces [n_faces,3] its faces, edited in
+ *   place; observed [n_vertices] is scratch of one byte per vertex.  A memset and two launches: per cell with an id in [0, V),
+ *   observed[id] = all 8 corner weights > 0 (a vertex no cell names stays unobserved); per face, (-1, -1, -1) when an index lies
+ *   outside [0, V) or names an unobserved vertex.  tn_mesh_filter with a threshold >= 1 then drops those faces and the vertices
+ *   they orphan.  Checked before any launch: TN_E_NULL for null dims, TN_E_SIZE for a negative dim or count or 2^31 nodes, vertices
+ *   or faces, TN_E_NULL, TN_E_ALIGN (4 bytes); n_faces == 0: TN_OK without a launch.
+ * No reference call site: the reference renders images and exports no geometry. */
+int tn_tsdf_integrate(const tn_camera_table *cams,
+                      const float *depth,                                       /* [n_pixels] device */
+                      const float *opacity,                                     /* [n_pixels] or NULL */
+                      float min_opacity,
+                      const int32_t *dims, const float *lo, const float *h,     /* host arrays of 3 */
+                      float trunc, int32_t view_first, int32_t view_count,
+                      float *S, float *W,                                       /* [(nx+1)(ny+1)(nz+1)] each */
+                      void *stream);
+int tn_tsdf_mask_faces(const float *W,                                          /* [(nx+1)(ny+1)(nz+1)] */
+                       const int32_t *dims,                                     /* host array of 3 */
+                       const int32_t *cell_ids,                                 /* [nx ny nz] */
+                       int64_t n_vertices,
+                       int32_t *faces,                                          /* [n_faces,3], edited in place */
+                       int64_t n_faces,
+                       uint8_t *observed,                                       /* [n_vertices] scratch */
+                       void *stream);
 
 /* ------------------------------------------------------------------------------------------
- * optimizer step of the harness                       (reference run.py:186,258-260: torch.optim.Adam)
+ * optimizer step of the harness                      (reference run.py:186,258-260: torch.optim.Adam)
  * One pass per parameter tensor: g' = g + wd*p (coupled L2, as torch), m = b1 m + (1-b1) g',
  * v = b2 v + (1-b2) g'^2, p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps); optionally zeroes g for the
  * next step.  28 B/element instead of torch's multi-kernel foreach path. */

@@ -50,7 +50,8 @@ SOURCES = {
     "mlp_f2_layers.hip": FAST + ["-munsafe-fp-atomics"],
     "mlp_fused_f2.hip": FAST,
     "mlp_b3_layers.hip": FAST + ["-munsafe-fp-atomics"],
-    "mesh_components.hip": FAST,      # mesh.hip's flags; last, so that the objects before it link where they did
+    "mesh_components.hip": FAST,      # mesh.hip's flags; after the training kernels, so that the objects before it link where they did
+    "tsdf.hip": FAST,                 # likewise
 }
 
 

@@ -1,0 +1,208 @@
+// Fusion of rendered depth maps into a truncated signed distance field on tn_mesh_extract's grid, and the mask that keeps the
+// extractor's faces out of cells no view has observed.  No reference call site: the reference renders images and exports
+// no geometry.
+//
+// Definition (include/tinynerf_hip.h has it in full) -- fp32 throughout, every fused multiply-add an explicit fmaf:
+//   node x_c = fmaf((float)idx_c, h_c, lo_c); per view, in ascending order:
+//     p = x - t, q = R^T p, z = -q_z > 0, (x', y') = (q_x, -q_y) / z                      camera frame, image axes y down
+//     (xd, yd) = the lens' forward model of (x', y'); skip unless 1 + 3 k1 s + 5 k2 s^2 + 7 k3 s^3 + 9 k4 s^4 > 0
+//     (u, v) = (fx xd + cx, fy yd + cy) inside [0, w) x [0, h); g = pixel_offset + floor(v) w + floor(u)
+//     D = depth[g] finite and > 0 (and opacity[g] >= min_opacity); sdf = D - |p| >= -trunc;  S += min(sdf / trunc, 1), W += 1
+//
+// tn_tsdf_integrate -- one launch: one lane per node (i fastest), 256 per workgroup, the loop over the views inside the kernel.  A
+//   view's table row (pose, lens, model, size, offset: 26 dwords) has a wave-uniform address and is read with scalar loads; what
+//   varies per lane is the node and the pixel it lands on.  Neighbouring nodes land on neighbouring pixels, so a wave's depth gather
+//   touches a few cache lines of one map.  No atomics: the lane owns its node's S and W, reads them once, adds the views in order
+//   and writes them once -- a range of views in one call and the same range split over calls give the same bytes.
+// tn_tsdf_mask_faces -- two launches: per cell whose id in the extractor's map is >= 0, observed[id] = all 8 corner weights > 0;
+//   per face, (-1, -1, -1) when an index lies outside [0, V) or names a vertex that is not observed.
+#include <cmath>
+#include "tn_common.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+
+struct TsdfGrid {
+    int sx, sy;                      // nodes on x and y: nx + 1, ny + 1
+    int64_t nodes;
+    float lo[3], h[3];
+    float trunc, min_opacity;
+};
+
+// 1 + s (c1 + s (c2 + s (c3 + s c4)))
+__device__ __forceinline__ float poly4(float s, float c1, float c2, float c3, float c4)
+{
+    return fmaf(s, fmaf(s, fmaf(s, fmaf(s, c4, c3), c2), c1), 1.0f);
+}
+
+__global__ __launch_bounds__(THREADS) void tsdf_integrate_kernel(tn_camera_table cams, const float *__restrict__ depth, const float *__restrict__ opacity,
+                                                                 TsdfGrid g, int view_first, int view_count, float *__restrict__ S,
+                                                                 float *__restrict__ W)
+{
+    const int64_t m = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (m >= g.nodes) return;
+    const uint32_t row = (uint32_t)m / (uint32_t)g.sx, k = row / (uint32_t)g.sy;
+    const float x0 = fmaf((float)((uint32_t)m - row * (uint32_t)g.sx), g.h[0], g.lo[0]);
+    const float x1 = fmaf((float)(row - k * (uint32_t)g.sy), g.h[1], g.lo[1]);
+    const float x2 = fmaf((float)k, g.h[2], g.lo[2]);
+    // (the table is read-only for the launch and `view` is the same in every lane: these become scalar loads)
+    const float *__restrict__ c2w = cams.c2w;
+    const float *__restrict__ lens = cams.lens;
+    const int32_t *__restrict__ models = cams.model;
+    const int32_t *__restrict__ sizes = cams.size;
+    const int64_t *__restrict__ offsets = cams.pixel_offset;
+    float s_sum = S[m], w_sum = W[m];
+    for (int view = view_first; view < view_first + view_count; ++view) {
+        const float *M = c2w + 12 * (int64_t)view;
+        const float p0 = x0 - M[3], p1 = x1 - M[7], p2 = x2 - M[11];
+        const float z = -fmaf(M[2], p0, fmaf(M[6], p1, M[10] * p2));
+        if (!(z > 0.0f)) continue;                                // behind the camera (or NaN)
+        const float qx = fmaf(M[0], p0, fmaf(M[4], p1, M[8] * p2)), qy = fmaf(M[1], p0, fmaf(M[5], p1, M[9] * p2));
+        const float xu = __fdiv_rn(qx, z), yu = __fdiv_rn(-qy, z);
+        const float *L = lens + 10 * (int64_t)view;
+        const int model = models[view];
+        float xd = xu, yd = yu;
+        if (model != TN_LENS_PINHOLE) {
+            const float k1 = L[4], k2 = L[5], k3 = L[6], k4 = L[7];
+            const float r2 = fmaf(xu, xu, yu * yu);
+            float s;                                              // what the radial polynomial is a polynomial of
+            if (model == TN_LENS_OPENCV) {
+                const float t1 = L[8], t2 = L[9], xy = xu * yu;
+                const float rad = poly4(r2, k1, k2, k3, k4);
+                xd = fmaf(xu, rad, fmaf(2.0f * t1, xy, t2 * fmaf(2.0f * xu, xu, r2)));
+                yd = fmaf(yu, rad, fmaf(2.0f * t2, xy, t1 * fmaf(2.0f * yu, yu, r2)));
+                s = r2;
+            } else {
+                const float r = sqrtf(r2), theta = atanf(r);
+                s = theta * theta;
+                const float scale = r > 0.0f ? __fdiv_rn(theta * poly4(s, k1, k2, k3, k4), r) : 1.0f;
+                xd = xu * scale, yd = yu * scale;
+            }
+            if (!(poly4(s, 3.0f * k1, 5.0f * k2, 7.0f * k3, 9.0f * k4) > 0.0f)) continue;      // the radial map has turned back here
+        }
+        const float u = fmaf(L[0], xd, L[2]), v = fmaf(L[1], yd, L[3]);
+        const int w = sizes[2 * view], h = sizes[2 * view + 1];
+        if (!(u >= 0.0f && u < (float)w && v >= 0.0f && v < (float)h)) continue;              // (NaN fails: nothing outside the map is read)
+        const int64_t px = offsets[view] + (int64_t)(int)v * w + (int)u;
+        const float D = depth[px];
+        if (!(D > 0.0f && isfinite(D))) continue;
+        if (opacity != nullptr && !(opacity[px] >= g.min_opacity)) continue;
+        const float sdf = D - sqrtf(fmaf(p0, p0, fmaf(p1, p1, p2 * p2)));
+        if (sdf < -g.trunc) continue;                             // hidden behind the surface in this view
+        s_sum += fminf(__fdiv_rn(sdf, g.trunc), 1.0f);
+        w_sum += 1.0f;
+    }
+    S[m] = s_sum;
+    W[m] = w_sum;
+}
+
+struct MaskGrid {
+    int nx, ny;
+    int64_t cells;
+};
+
+__global__ __launch_bounds__(THREADS) void tsdf_observed_kernel(const float *__restrict__ W, MaskGrid g, const int32_t *__restrict__ cell_ids,
+                                                                int32_t n_vertices, uint8_t *__restrict__ observed)
+{
+    const int64_t c = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (c >= g.cells) return;
+    const int32_t id = cell_ids[c];
+    if ((uint32_t)id >= (uint32_t)n_vertices) return;             // -1: no vertex; an id that is not the extractor's writes nothing
+    const uint32_t row = (uint32_t)c / (uint32_t)g.nx, k = row / (uint32_t)g.ny;
+    const int64_t sy = (int64_t)g.nx + 1, sz = sy * ((int64_t)g.ny + 1);
+    const int64_t node = ((uint32_t)c - row * (uint32_t)g.nx) + sy * (row - k * (uint32_t)g.ny) + sz * k;
+    bool all = true;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) all = all && W[node + (d & 1) + ((d >> 1) & 1) * sy + (d >> 2) * sz] > 0.0f;
+    observed[id] = all ? 1 : 0;
+}
+
+__global__ __launch_bounds__(THREADS) void tsdf_mask_kernel(const uint8_t *__restrict__ observed, int32_t n_vertices, int64_t n_faces,
+                                                            int32_t *__restrict__ faces)
+{
+    const int64_t f = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    if (f >= n_faces) return;
+    bool keep = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int32_t v = faces[3 * f + k];
+        keep = keep && (uint32_t)v < (uint32_t)n_vertices && observed[(uint32_t)v < (uint32_t)n_vertices ? v : 0] != 0;
+    }
+    if (!keep) faces[3 * f] = -1, faces[3 * f + 1] = -1, faces[3 * f + 2] = -1;
+}
+
+int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// the number of a grid's nodes (cells = false) or cells, 0 with an empty axis, -1 for a negative dim or 2^31 or more
+int64_t grid_count(const int32_t *dims, bool cells)
+{
+    const int64_t limit = (int64_t)1 << 31;
+    if (dims[0] < 0 || dims[1] < 0 || dims[2] < 0) return -1;
+    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0) return 0;
+    const int64_t e = cells ? 0 : 1, xy = (dims[0] + e) * (dims[1] + e);      // (< 2^62)
+    if (xy >= limit || xy * (dims[2] + e) >= limit) return -1;
+    return xy * (dims[2] + e);
+}
+
+}  // namespace
+
+extern "C" int tn_tsdf_integrate(const tn_camera_table *cams, const float *depth, const float *opacity, float min_opacity, const int32_t *dims,
+                                 const float *lo, const float *h, float trunc, int32_t view_first, int32_t view_count, float *S, float *W,
+                                 void *stream)
+{
+    TN_REQUIRE(cams && dims && lo && h, TN_E_NULL, "tn_tsdf_integrate: null pointer (cams, dims, lo, h)");
+    const int64_t nodes = grid_count(dims, false);
+    TN_REQUIRE(nodes >= 0, TN_E_SIZE, "tn_tsdf_integrate: dims must be >= 0 with fewer than 2^31 nodes");
+    TN_REQUIRE(view_first >= 0 && view_count >= 0 && cams->n_img >= 0 && view_count <= cams->n_img && view_first <= cams->n_img - view_count, TN_E_SIZE,
+               "tn_tsdf_integrate: view_first .. view_first + view_count must lie inside the camera table");
+    TN_REQUIRE(std::isfinite(trunc) && trunc > 0.0f, TN_E_CONFIG, "tn_tsdf_integrate: trunc must be finite and > 0");
+    if (view_count == 0 || nodes == 0) return TN_OK;
+    TN_REQUIRE(cams->c2w && cams->lens && cams->model && cams->size && cams->pixel_offset, TN_E_NULL,
+               "tn_tsdf_integrate: null pointer in the camera table (rgb is not read)");
+    TN_REQUIRE(depth && S && W, TN_E_NULL, "tn_tsdf_integrate: null pointer (depth, S, W)");
+    TN_REQUIRE(((uintptr_t)depth & 3) == 0 && ((uintptr_t)opacity & 3) == 0 && ((uintptr_t)S & 3) == 0 && ((uintptr_t)W & 3) == 0, TN_E_ALIGN,
+               "tn_tsdf_integrate: depth, opacity, S and W must be 4-byte aligned");
+    TsdfGrid g;
+    g.sx = dims[0] + 1, g.sy = dims[1] + 1;
+    g.nodes = nodes;
+    for (int a = 0; a < 3; ++a) g.lo[a] = lo[a], g.h[a] = h[a];
+    g.trunc = trunc, g.min_opacity = min_opacity;
+    tsdf_integrate_kernel<<<dim3((unsigned)ceil_div(nodes, THREADS)), dim3(THREADS), 0, (hipStream_t)stream>>>(*cams, depth, opacity, g, view_first,
+                                                                                                           view_count, S, W);
+    return tn::check_launch("tsdf_integrate_kernel");
+}
+
+extern "C" int tn_tsdf_mask_faces(const float *W, const int32_t *dims, const int32_t *cell_ids, int64_t n_vertices, int32_t *faces, int64_t n_faces,
+                                  uint8_t *observed, void *stream)
+{
+    TN_REQUIRE(dims, TN_E_NULL, "tn_tsdf_mask_faces: null pointer (dims)");
+    const int64_t cells = grid_count(dims, true), limit = (int64_t)1 << 31;
+    TN_REQUIRE(cells >= 0 && grid_count(dims, false) >= 0, TN_E_SIZE, "tn_tsdf_mask_faces: dims must be >= 0 with fewer than 2^31 nodes");
+    TN_REQUIRE(n_vertices >= 0 && n_faces >= 0 && n_vertices < limit && n_faces < limit, TN_E_SIZE,
+               "tn_tsdf_mask_faces: n_vertices and n_faces must be >= 0 and below 2^31 (vertex ids are int32)");
+    if (n_faces == 0) return TN_OK;
+    TN_REQUIRE(faces, TN_E_NULL, "tn_tsdf_mask_faces: null pointer (faces)");
+    TN_REQUIRE(n_vertices == 0 || observed, TN_E_NULL, "tn_tsdf_mask_faces: null pointer (observed)");
+    TN_REQUIRE(n_vertices == 0 || cells == 0 || (W && cell_ids), TN_E_NULL, "tn_tsdf_mask_faces: null pointer (W, cell_ids)");
+    TN_REQUIRE(((uintptr_t)W & 3) == 0 && ((uintptr_t)cell_ids & 3) == 0 && ((uintptr_t)faces & 3) == 0, TN_E_ALIGN,
+               "tn_tsdf_mask_faces: W, cell_ids and faces must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (n_vertices > 0) {
+        hipError_t e = hipMemsetAsync(observed, 0, (size_t)n_vertices, s);      // a vertex no cell names is not observed
+        if (e != hipSuccess) {
+            tn::set_error("tn_tsdf_mask_faces: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+        if (cells > 0) {
+            MaskGrid g;
+            g.nx = dims[0], g.ny = dims[1];
+            g.cells = cells;
+            tsdf_observed_kernel<<<dim3((unsigned)ceil_div(cells, THREADS)), dim3(THREADS), 0, s>>>(W, g, cell_ids, (int32_t)n_vertices, observed);
+            const int rc = tn::check_launch("tsdf_observed_kernel");
+            if (rc != TN_OK) return rc;
+        }
+    }
+    tsdf_mask_kernel<<<dim3((unsigned)ceil_div(n_faces, THREADS)), dim3(THREADS), 0, s>>>(observed, (int32_t)n_vertices, n_faces, faces);
+    return tn::check_launch("tsdf_mask_kernel");
+}

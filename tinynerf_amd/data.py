@@ -72,6 +72,7 @@ class PoseDataset:
 
     def __init__(self, data: NerfData, device: torch.device | str = "cpu"):
         self.rays_o, self.rays_d = data.generate_rays(device)
+        self.cameras = data.cameras                # [n, 4, 4] on the host: a pose-only camera table can be made of the split (tsdf.camera_table)
         self.rgbs = None if data.imgs is None else [_as_float(im).to(device) for im in data.imgs]
         self.scene_scale = data.scene_scale()
         self.bg_color = data.bg_color

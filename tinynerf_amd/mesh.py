@@ -2,7 +2,7 @@
 set extracted by naive Surface Nets on the device -- one vertex per cell the surface passes through, one quad per grid edge it
 crosses; an indexed mesh, closed and consistently oriented wherever the surface does not reach the box --, written as a PLY.
 
-* ``extract`` -- ``tn_mesh_extract`` over a tensor of node values: vertices, normals, faces;
+* ``extract`` -- ``tn_mesh_extract`` over a tensor of node values: vertices, normals, faces; ``extract_with_cells`` -- and the cell -> vertex id map;
 * ``density_grid`` / ``extract_mesh`` -- the node values of a trainer / of any density callable, and their mesh;
 * ``export_mesh`` -- a trainer's mesh with vertex colours from its colour decoder, written to ``path``;
 * ``write_mesh_ply`` / ``read_mesh_ply`` -- binary little-endian PLY, 27 B per vertex, 13 B per face.
@@ -56,6 +56,16 @@ def extract(values: torch.Tensor, lo, h, level: float, normals: bool = True, cap
     grid of ``nx x ny x nz`` cells (include/tinynerf_hip.h has the definition).  The normals point from inside to outside.
     ``capacity=None``: a count-only call, one read-back, then the call that writes; ``(vertex rows, face rows)``: one call into buffers
     of that size -- at most that many rows come back (the first ones), the faces still naming the full mesh's vertices."""
+    return _extract(values, lo, h, level, normals, capacity, False)
+
+
+def extract_with_cells(values: torch.Tensor, lo, h, level: float, normals: bool = True, capacity: Optional[Tuple[int, int]] = None):
+    """``extract`` with a fourth entry, ``cell_ids [nz, ny, nx] int32``: every cell's vertex id, -1 for a cell without a vertex -- a
+    copy of the map the extractor leaves in its workspace (``tsdf.mask_faces`` reads it)"""
+    return _extract(values, lo, h, level, normals, capacity, True)
+
+
+def _extract(values, lo, h, level, normals, capacity, return_cells):
     if values.dim() != 3 or min(values.shape) < 1:
         raise ValueError("extract: values must be [nz+1, ny+1, nx+1]")
     v = values if values.dtype == torch.float32 and values.is_contiguous() else values.float().contiguous()
@@ -75,17 +85,27 @@ def extract(values: torch.Tensor, lo, h, level: float, normals: bool = True, cap
                L.ptr(vert) if vcap else None, L.ptr(nrm) if vcap else None, L.ptr(faces) if fcap else None, L.ptr(counts), L.ptr(workspace))
         return vert, nrm, faces
 
+    def cells(written: bool):
+        """the id map: behind the ballots and counts of ceil(cells / 256) workgroups, 144 B each; only a call with a capacity > 0 writes it"""
+        n = dims[0] * dims[1] * dims[2]
+        if not written or n == 0:
+            return torch.full((dims[2], dims[1], dims[0]), -1, dtype=torch.int32, device=dev)
+        first = 144 * (-(-n // 256))
+        return workspace[first:first + 4 * n].view(torch.int32).view(dims[2], dims[1], dims[0]).clone()
+
     if capacity is None:
         run(0, 0)
         n_v, n_f = counts.tolist()
-        return run(n_v, n_f)
+        out = run(n_v, n_f)
+        return out + (cells(n_v > 0 or n_f > 0),) if return_cells else out
     vcap, fcap = int(capacity[0]), int(capacity[1])
     if vcap < 0 or fcap < 0:
         raise ValueError("extract: capacity must be >= 0")
     vert, nrm, faces = run(vcap, fcap)
     n_v, n_f = counts.tolist()
     n_v, n_f = min(n_v, vcap), min(n_f, fcap)
-    return vert[:n_v], None if nrm is None else nrm[:n_v], faces[:n_f]
+    out = vert[:n_v], None if nrm is None else nrm[:n_v], faces[:n_f]
+    return out + (cells(vcap > 0 or fcap > 0),) if return_cells else out
 
 
 def grid_dims(box, resolution: int):

@@ -938,7 +938,7 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
           eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
           render_maps: bool = False, ssim: bool = False, pointcloud: int = 0, pointcloud_crop=None,
           mesh: int = 0, mesh_level: Optional[float] = None, mesh_crop=None, mesh_min_faces: int = 0, mesh_keep_fraction: float = 0.0,
-          normals: bool = False):
+          tsdf_mesh: int = 0, tsdf_trunc: Optional[float] = None, normals: bool = False):
     """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device, or a data.CameraRaysDataset (a
     photographed scene: the trainer makes its rays from the camera table, ``Trainer(ray_source=...)``).  ``render_maps``: the final
     test render also writes the depth / opacity maps of every image (``infer(maps=True)``).  ``ssim``: the periodic evaluation and
@@ -952,7 +952,11 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
     on the longest axis of the box (``mesh.export_mesh``; ``mesh_level``, ``mesh_crop``: its ``level`` and ``crop``).  At 0
     nothing of it is imported, allocated or launched.  ``mesh_min_faces`` / ``mesh_keep_fraction``: when one of them is not 0 the mesh
     goes through ``mesh.export_clean_mesh`` instead -- only the connected components with at least ``max(mesh_min_faces,
-    ceil(mesh_keep_fraction x the largest component's faces))`` faces are written; with both 0 ``export_mesh`` is called as before."""
+    ceil(mesh_keep_fraction x the largest component's faces))`` faces are written; with both 0 ``export_mesh`` is called as before.
+    ``tsdf_mesh`` > 0 (with `test_set` and `output`): after the final test render the test views' depth maps are fused into a TSDF and
+    its zero level goes to ``tsdf_mesh.ply``, ``tsdf_mesh`` cells on the longest axis of the box (``tsdf.export_tsdf_mesh``, DESIGN 6j;
+    ``tsdf_trunc``: its ``trunc``; ``mesh_crop``, ``mesh_min_faces`` and ``mesh_keep_fraction`` apply to it as well).  At 0 nothing of
+    it is imported, allocated or launched."""
     import json
     if normals and cfg.method not in ("kplanes", "hashgrid"):
         raise ValueError(f"train(normals=True): method {cfg.method!r} has no analytic density gradient (kplanes and hashgrid only)")
@@ -1000,6 +1004,10 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
             else:
                 from .mesh import export_mesh
                 export_mesh(tr, output / "mesh.ply", resolution=mesh, level=mesh_level, crop=mesh_crop)
+        if tsdf_mesh > 0 and output is not None:
+            from .tsdf import export_tsdf_mesh
+            export_tsdf_mesh(tr, test_set, output / "tsdf_mesh.ply", resolution=tsdf_mesh, trunc=tsdf_trunc, crop=mesh_crop,
+                             min_faces=mesh_min_faces, keep_fraction=mesh_keep_fraction)
         if render_maps:
             rendered = [r["rgb"] for r in rendered]
         if test_set.rgbs:

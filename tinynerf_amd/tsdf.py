@@ -1,0 +1,167 @@
+"""Triangle mesh of what the model RENDERS: the depth maps of known cameras fused into a truncated signed distance field
+on ``mesh.extract``'s grid, its zero level extracted, the cells no view has observed masked out, small pieces dropped.  Against the
+level set of the raw density (``mesh.export_mesh``) the level is 0 whatever the grid, the depth along a ray is already a weighted sum
+over the whole ray, so fog averages out, and views that disagree vote.
+
+* ``integrate`` -- ``tn_tsdf_integrate``: the views of a camera table and their depth maps added into ``(S, W)``;
+* ``field`` -- the mesh field ``-S / W`` (``-1`` where ``W == 0``), level 0, inside ``>= 0``;
+* ``mask_faces`` -- ``tn_tsdf_mask_faces``: faces of cells with an unobserved corner become ``(-1, -1, -1)``;
+* ``camera_table`` -- the pose-only ``rays.CameraRays`` of a ``PoseDataset`` / ``CameraPoseDataset``;
+* ``export_tsdf_mesh`` -- render, integrate, extract, mask, filter, colour, write.
+
+torch is plumbing only; there is no CPU path.  No reference counterpart: the reference renders images and exports no geometry.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .mesh import _grid
+from .rays import CameraRays
+
+# Views per launch.  Every split gives the same bytes (the definition), so this is a matter of time alone: all views in one launch make
+# every workgroup sweep every map, chunks cost 8 B of read-modify-write per node and launch.  Measured (scripts/tsdf_time.py):
+# 100 views of 200 x 200 into 257^3 nodes take 6.3 ms in one launch, 3.3 ms at 16 views per launch, 6.4 ms at one view per launch.
+VIEWS_PER_LAUNCH = 16
+
+
+def _box_grid(box, dims):
+    """``(lo, h)`` as float32, the way ``mesh.density_grid`` cuts a box into ``dims`` cells"""
+    box = np.asarray(box, np.float64).reshape(6)
+    dims = tuple(int(d) for d in dims)
+    if len(dims) != 3 or min(dims) < 0:
+        raise ValueError("tsdf: dims must be three cell counts >= 0")
+    if not np.isfinite(box).all() or not (box[3:] > box[:3]).all():
+        raise ValueError("tsdf: the box must be finite with a positive extent on every axis")
+    return box[:3].astype(np.float32), ((box[3:] - box[:3]) / np.maximum(np.float64(dims), 1.0)).astype(np.float32), dims
+
+
+def integrate(cams: CameraRays, depth: torch.Tensor, opacity: Optional[torch.Tensor], box, dims: Sequence[int], trunc: float,
+              min_opacity: float = 0.5, state: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+              views: Optional[Tuple[int, int]] = None):
+    """``(S, W)``, float32 ``[nz+1, ny+1, nx+1]`` each, on the device: the views of the camera table ``cams`` added into the TSDF on
+    the grid of ``box`` (lo xyz, hi xyz) cut into ``dims = (nx, ny, nz)`` cells (include/tinynerf_hip.h has the definition).  ``depth``
+    holds one distance along the unit ray per pixel of the table, in its flat pixel order; ``opacity`` likewise, or ``None`` (then
+    ``min_opacity`` is not used).  ``state``: the ``(S, W)`` of an earlier call, added to IN PLACE (``None``: zeros).  ``views``:
+    ``(first, count)`` (``None``: all).  The views go to the kernel ``VIEWS_PER_LAUNCH`` at a time; every split gives the same bytes."""
+    lo, h, dims = _box_grid(box, dims)
+    if not (math.isfinite(float(trunc)) and float(trunc) > 0.0):
+        raise ValueError("tsdf.integrate: trunc must be finite and > 0")
+    first, count = (0, cams.n_img) if views is None else (int(views[0]), int(views[1]))
+    if first < 0 or count < 0 or first + count > cams.n_img:
+        raise ValueError("tsdf.integrate: views must lie inside the camera table")
+    if depth.numel() != cams.n_rays or (opacity is not None and opacity.numel() != cams.n_rays):
+        raise ValueError("tsdf.integrate: depth and opacity must hold one entry per pixel of the camera table")
+    if depth.dtype != torch.float32 or (opacity is not None and opacity.dtype != torch.float32):
+        raise ValueError("tsdf.integrate: depth and opacity must be float32")
+    shape = (dims[2] + 1, dims[1] + 1, dims[0] + 1)
+    dev = L.require_cuda(cams.c2w, depth, opacity)
+    if state is None:
+        S, W = torch.zeros(shape, dtype=torch.float32, device=dev), torch.zeros(shape, dtype=torch.float32, device=dev)
+    else:
+        S, W = state
+        if tuple(S.shape) != shape or tuple(W.shape) != shape or S.dtype != torch.float32 or W.dtype != torch.float32:
+            raise ValueError("tsdf.integrate: state must be two float32 tensors [nz+1, ny+1, nx+1]")
+        L.require_cuda(S, W, depth)
+    lo_c, h_c, dims_c = _grid(lo, h, dims)
+    for v in range(first, first + count, VIEWS_PER_LAUNCH):
+        L.call("tn_tsdf_integrate", dev, C.byref(cams.table), L.ptr(depth), L.ptr(opacity), C.c_float(min_opacity), dims_c, lo_c, h_c,
+               C.c_float(trunc), C.c_int32(v), C.c_int32(min(VIEWS_PER_LAUNCH, first + count - v)), L.ptr(S), L.ptr(W))
+    return S, W
+
+
+def field(S: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
+    """the mesh field of a TSDF: ``-S / W`` where ``W > 0``, ``-1`` (empty) elsewhere; the surface is its level 0, inside ``>= 0``"""
+    seen = W > 0
+    return torch.where(seen, -S / torch.where(seen, W, torch.ones_like(W)), torch.full_like(S, -1.0))
+
+
+def mask_faces(W: torch.Tensor, dims: Sequence[int], cell_ids: torch.Tensor, n_vertices: int, faces: torch.Tensor) -> torch.Tensor:
+    """a copy of ``faces [F,3] int32`` in which every face that names a vertex of a cell with an unobserved corner (``W == 0``), or an
+    index outside ``[0, n_vertices)``, is ``(-1, -1, -1)`` (``tn_tsdf_mask_faces``); ``cell_ids`` is ``mesh.extract_with_cells``'s
+    map.  ``mesh.filter_components(min_faces >= 1)`` then drops those faces and the vertices they orphan."""
+    dims = tuple(int(d) for d in dims)
+    V = int(n_vertices)
+    if faces.dim() != 2 or faces.size(1) != 3 or faces.dtype != torch.int32 or V < 0:
+        raise ValueError("mask_faces: faces must be [F,3] int32 and n_vertices >= 0")
+    if len(dims) != 3 or min(dims) < 0 or W.dtype != torch.float32 or W.numel() != (dims[0] + 1) * (dims[1] + 1) * (dims[2] + 1):
+        raise ValueError("mask_faces: W must be float32 with one entry per node of dims")
+    if cell_ids.dtype != torch.int32 or cell_ids.numel() != dims[0] * dims[1] * dims[2]:
+        raise ValueError("mask_faces: cell_ids must be int32 with one entry per cell of dims")
+    dev = L.require_cuda(W, cell_ids, faces)
+    out = faces.clone()
+    observed = torch.empty(max(V, 1), dtype=torch.uint8, device=dev)
+    L.call("tn_tsdf_mask_faces", dev, L.ptr(W), (C.c_int32 * 3)(*dims), L.ptr(cell_ids) if cell_ids.numel() else None,
+           C.c_int64(V), L.ptr(out) if out.size(0) else None, C.c_int64(out.size(0)), L.ptr(observed))
+    return out
+
+
+def camera_table(dataset, indices: Optional[Sequence[int]] = None, device=None) -> CameraRays:
+    """the pose-only camera table (no colours) of the views ``indices`` (``None``: all) of a ``data.PoseDataset`` -- one pinhole camera,
+    its poses kept as ``cameras`` -- or a ``data.CameraPoseDataset`` -- the rows of its ``source``"""
+    src = getattr(dataset, "source", None)
+    idx = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+    if src is not None:
+        sel = torch.as_tensor(idx, dtype=torch.long)
+        return CameraRays(src.c2w.cpu()[sel], src.lens.cpu()[sel], src.model.cpu()[sel], src.size.cpu()[sel], None, device or src.device)
+    if not hasattr(dataset, "cameras"):
+        raise ValueError("tsdf: the dataset must be a data.PoseDataset or a data.CameraPoseDataset")
+    K = [dataset.img_intrinsics(i) for i in idx]
+    lens = torch.zeros((len(idx), 10), dtype=torch.float32)
+    if idx:
+        lens[:, :4] = torch.tensor([[k.fx, k.fy, k.cx, k.cy] for k in K], dtype=torch.float64).float()
+    return CameraRays(dataset.cameras[idx][:, :3, :], lens, [0] * len(idx), [[k.w, k.h] for k in K], None, device or dataset.rays_o.device)
+
+
+@torch.no_grad()
+def export_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: Optional[float] = None, crop=None,
+                     indices: Optional[Sequence[int]] = None, min_faces: int = 0, keep_fraction: float = 0.0, depth: str = "expected",
+                     colors: bool = True):
+    """The mesh of what the trainer renders from the views ``indices`` (``None``: all) of ``dataset`` (a ``PoseDataset`` or a
+    ``CameraPoseDataset``): every view rendered through ``render_rays(maps=True)``, its ``depth`` (``"expected"`` or ``"median"``) and
+    opacity integrated into a TSDF on ``mesh.grid_dims(crop, resolution)`` (``crop`` ``None``: ``points.default_crop``) with the
+    truncation ``trunc`` (``None``: ``4 max(h)``), the zero level extracted (``mesh.extract``), the faces of unobserved cells masked,
+    and ``mesh.filter_components(max(1, min_faces), keep_fraction)`` -- which drops the masked faces and orphaned vertices, and the
+    pieces below the threshold.  Returns ``(vertices, normals, colors, faces)`` on the device as ``mesh.export_mesh`` does -- colours
+    from ``mesh.vertex_colors``, zeros when switched off -- and writes ``path`` (``mesh.write_mesh_ply``) when one is given."""
+    if getattr(trainer, "world", 1) > 1:
+        raise ValueError("export_tsdf_mesh runs on one rank: world_size > 1 is not supported")
+    from . import mesh as M
+    from .points import DEPTH_KEYS, default_crop
+    M.component_threshold(min_faces, keep_fraction, 0)             # the arguments, before any device work
+    if depth not in DEPTH_KEYS:
+        raise ValueError(f"export_tsdf_mesh: depth must be one of {sorted(DEPTH_KEYS)}, not {depth!r}")
+    box = default_crop(trainer.cfg) if crop is None else crop
+    lo, h, dims = M.grid_dims(box, resolution)
+    trunc = 4.0 * float(np.max(h)) if trunc is None else float(trunc)
+    if not (math.isfinite(trunc) and trunc > 0.0):
+        raise ValueError("export_tsdf_mesh: trunc must be finite and > 0")
+    idx = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+    dev = trainer.device
+    S = torch.zeros((dims[2] + 1, dims[1] + 1, dims[0] + 1), dtype=torch.float32, device=dev)
+    W = torch.zeros_like(S)
+    if idx:
+        cams = camera_table(dataset, idx, dev)
+        dist = torch.empty(cams.n_rays, dtype=torch.float32, device=dev)
+        opacity = torch.empty(cams.n_rays, dtype=torch.float32, device=dev)
+        for k, i in enumerate(idx):
+            item = dataset[i]
+            o, d = item["rays_o"].reshape(-1, 3).to(dev), item["rays_d"].reshape(-1, 3).to(dev)
+            if o.size(0) != cams.offsets[k + 1] - cams.offsets[k]:
+                raise RuntimeError("export_tsdf_mesh: a view's rays do not match the size its camera states")
+            maps = trainer.render_rays(o, d, maps=True)
+            dist[cams.offsets[k]:cams.offsets[k + 1]] = maps[DEPTH_KEYS[depth]].reshape(-1)
+            opacity[cams.offsets[k]:cams.offsets[k + 1]] = maps["opacity"].reshape(-1)
+        integrate(cams, dist, opacity, box, dims, trunc, state=(S, W))          # (the same box and dims: grid_dims' lo and h, bit for bit)
+    vertices, normals, faces, cells = M.extract_with_cells(field(S, W), lo, h, 0.0)
+    faces = mask_faces(W, dims, cells, vertices.size(0), faces)
+    vertices, normals, _, faces = M.filter_components(vertices, normals, None, faces, min_faces=max(1, int(min_faces)), keep_fraction=keep_fraction)
+    rgb = M.vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=dev)
+    if path is not None:
+        M.write_mesh_ply(path, vertices, normals, rgb, faces)
+    return vertices, normals, rgb, faces

@@ -13,7 +13,8 @@ import uuid
 from pathlib import Path
 
 # (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight, --ssim,
-# --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop, --normals, --export_mesh, --mesh_level, --mesh_crop, --mesh_min_faces and --mesh_keep_fraction
+# --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop, --normals, --export_mesh, --mesh_level, --mesh_crop, --mesh_min_faces, --mesh_keep_fraction,
+# --export_tsdf_mesh and --tsdf_trunc
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -43,6 +44,10 @@ FLAGS = (
     ("--mesh_min_faces", dict(type=int, default=0, metavar="N", help="with --export_mesh: drop the connected pieces of the mesh with fewer than N triangles (0: keep all)")),
     ("--mesh_keep_fraction", dict(type=float, default=0.0, metavar="F", help="with --export_mesh: drop the pieces with fewer than F x the largest piece's triangles "
                                                                                "(1.0: the largest piece alone; 0: keep all)")),
+    ("--export_tsdf_mesh", dict(type=int, default=0, metavar="R", help="write tsdf_mesh.ply: the test views' depth maps fused into a truncated signed distance "
+                                                                        "field, its zero level as a triangle mesh, R cells on the longest axis of the box (0: off); "
+                                                                        "--mesh_crop, --mesh_min_faces and --mesh_keep_fraction apply to it too")),
+    ("--tsdf_trunc", dict(type=float, default=None, metavar="T", help="with --export_tsdf_mesh: the truncation distance (default: 4 cells)")),
 )
 
 
@@ -53,10 +58,14 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.normals and args.method not in ("kplanes", "hashgrid"):
         parser.error(f"--normals needs --method kplanes or hashgrid: {args.method} has no analytic density gradient")
-    if (args.mesh_min_faces or args.mesh_keep_fraction) and not args.export_mesh:
-        parser.error("--mesh_min_faces and --mesh_keep_fraction filter the mesh of --export_mesh R: give that too")
+    if (args.mesh_min_faces or args.mesh_keep_fraction) and not (args.export_mesh or args.export_tsdf_mesh):
+        parser.error("--mesh_min_faces and --mesh_keep_fraction filter the mesh of --export_mesh R or --export_tsdf_mesh R: give one of them too")
     if args.mesh_min_faces < 0 or not 0.0 <= args.mesh_keep_fraction <= 1.0:
         parser.error("--mesh_min_faces must be >= 0 and --mesh_keep_fraction lie in [0, 1]")
+    if args.tsdf_trunc is not None and not args.export_tsdf_mesh:
+        parser.error("--tsdf_trunc is the truncation of --export_tsdf_mesh R: give that too")
+    if args.export_tsdf_mesh < 0 or (args.tsdf_trunc is not None and not 0.0 < args.tsdf_trunc < float("inf")):
+        parser.error("--export_tsdf_mesh must be >= 0 and --tsdf_trunc finite and > 0")
     return args
 
 
@@ -115,7 +124,7 @@ def main(argv=None):
     train(cfg, train_rays, eval_set, test_set, run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim,
           pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop, normals=args.normals,
           mesh=args.export_mesh, mesh_level=args.mesh_level, mesh_crop=args.mesh_crop, mesh_min_faces=args.mesh_min_faces,
-          mesh_keep_fraction=args.mesh_keep_fraction)
+          mesh_keep_fraction=args.mesh_keep_fraction, tsdf_mesh=args.export_tsdf_mesh, tsdf_trunc=args.tsdf_trunc)
 
 
 if __name__ == "__main__":
