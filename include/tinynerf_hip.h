@@ -709,7 +709,8 @@ int tn_camera_rays(const tn_camera_table *cams, const int32_t *idx, int64_t firs
  * of kept rays whatever `capacity` is; rows k >= capacity are not written and no row at or beyond min(count, capacity) is touched;
  * with capacity == 0 the three output pointers may be NULL (count only).  Three launches on `stream` (per-wave ballots, one
  * workgroup scanning the workgroup counts, ranked stores), no atomics: the same bytes on every call.  `workspace`:
- * tn_points_workspace_bytes(n) bytes, 8-byte aligned like `count` (TN_E_ALIGN otherwise); contents undefined afterwards.
+ * tn_points_workspace_bytes(n) = 40 ceil(n / 256) bytes (per workgroup of 256 rays 4 waves x 1 ballot of 8 B, then the workgroup
+ * counts of 8 B: the layout of the mesh workspaces below), 8-byte aligned like `count` (TN_E_ALIGN otherwise); contents undefined afterwards.
  * Checked before any launch: TN_E_SIZE for n < 0, capacity < 0 or n >= 2^31 (src is int32); TN_E_CONFIG unless min_opacity > 0
  * (NaN included: the division stays defined); TN_E_NULL for a null required pointer (bg and box are optional; the inputs and the
  * workspace are not read for n == 0).  n == 0 writes *count = 0 and returns TN_OK.  No reference call site: the reference renders

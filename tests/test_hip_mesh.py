@@ -23,9 +23,10 @@ SENTINEL_F, SENTINEL_I, TAIL = -7.25, -12345, 5
 
 
 # ------------------------------------------------------------------------------------------------------------ the call
-def run(values, lo, h, level, vcap, fcap, alloc=None, null_outputs=False, normals=True):
+def run(values, lo, h, level, vcap, fcap, alloc=None, null_outputs=False, normals=True, guard=(0, 64), spare=0):
     """tn_mesh_extract through the C ABI on sentinel-filled outputs of `alloc` = (vertex rows, face rows) >= the capacities ->
-    (counts, vertices, normals, faces, cell -> vertex id map) as numpy, ALL allocated rows"""
+    (counts, vertices, normals, faces, cell -> vertex id map) as numpy, ALL allocated rows.  The workspace is
+    tn_mesh_workspace_bytes + `spare` bytes with `guard` bytes of a fixed pattern before and behind it."""
     from tinynerf_amd import _lib as L
     dev = torch.device(DEV)
     v = torch.from_numpy(np.array(values, np.float32)).to(dev)              # (a copy: the shared case is read only)
@@ -36,18 +37,19 @@ def run(values, lo, h, level, vcap, fcap, alloc=None, null_outputs=False, normal
     lo_c, h_c, dims_c = (C.c_float * 3)(*np.float32(lo).tolist()), (C.c_float * 3)(*np.float32(h).tolist()), (C.c_int32 * 3)(nx, ny, nz)
     nbytes = C.c_int64(0)
     L.call_plain("tn_mesh_workspace_bytes", C.c_int32(nx), C.c_int32(ny), C.c_int32(nz), C.byref(nbytes))
-    work = torch.full((nbytes.value + 64,), 0x5A, dtype=torch.uint8, device=dev)              # 64 guard bytes behind the workspace
+    first, last = guard[0], guard[0] + nbytes.value + spare
+    work = torch.full((last + guard[1],), 0x5A, dtype=torch.uint8, device=dev)
     vert = torch.full((va, 3), SENTINEL_F, dtype=torch.float32, device=dev)
     nrm = torch.full((va, 3), SENTINEL_F, dtype=torch.float32, device=dev)
     faces = torch.full((fa, 3), SENTINEL_I, dtype=torch.int32, device=dev)
     counts = torch.full((2,), -1, dtype=torch.int64, device=dev)
     outs = (None, None, None) if null_outputs else (L.ptr(vert), L.ptr(nrm) if normals else None, L.ptr(faces))
     L.call("tn_mesh_extract", dev, L.ptr(v), dims_c, lo_c, h_c, C.c_float(level), C.c_int64(vcap), C.c_int64(fcap), *outs, L.ptr(counts),
-           L.ptr(work))
+           L.ptr(work[first:]))
     torch.cuda.synchronize()
-    assert bool((work[nbytes.value:] == 0x5A).all()), "the workspace was overrun"
+    assert bool((work[:first] == 0x5A).all()) and bool((work[last:] == 0x5A).all()), "the workspace was overrun"
     g = -(-cells // 256)
-    vid = work[144 * g:144 * g + 4 * cells].cpu().numpy().view(np.int32)          # the documented layout: ballots, counts, then the ids
+    vid = work[first + 144 * g:first + 144 * g + 4 * cells].cpu().numpy().view(np.int32)      # the documented layout: ballots, counts, then the ids
     return counts.cpu().numpy(), vert.cpu().numpy(), nrm.cpu().numpy(), faces.cpu().numpy(), vid
 
 
@@ -115,6 +117,19 @@ def test_counts_cells_faces_exact_positions_and_normals_within_bounds(name, dims
         want = ref.case(name, dims)[4]
         vol, vol_ref = ref.signed_volume(vert, faces), ref.signed_volume(want["vertices"], want["faces"])
         assert vol > 0 and abs(vol - vol_ref) <= 1e-5 * vol_ref, (vol, vol_ref)
+
+
+@pytest.mark.parametrize("dims", [(1, 1, 1), (3, 5, 7), (17, 9, 33)])
+def test_the_workspace_is_what_the_size_function_says(dims):
+    """every ballot, count and id lands inside the layout: a workspace of exactly tn_mesh_workspace_bytes in the middle of a larger
+    buffer leaves the bytes around it alone (`run` asserts that) and gives the outputs, the id map included, of a generous one"""
+    for name in ("noise", "sphere"):
+        values, lo, h, level, want = ref.case(name, dims)
+        V, F = want["vertices"].shape[0], want["faces"].shape[0]
+        tight = run(values, lo, h, level, V, F, alloc=(V + TAIL, F + TAIL), guard=(256, 256))
+        generous = run(values, lo, h, level, V, F, alloc=(V + TAIL, F + TAIL), guard=(256, 256), spare=4096)
+        assert tight[0].tolist() == [V, F], (name, dims)
+        assert all(np.array_equal(a.view(np.uint8), b.view(np.uint8)) for a, b in zip(tight, generous)), (name, dims)
 
 
 def test_two_calls_give_the_same_bytes_and_normals_are_optional():

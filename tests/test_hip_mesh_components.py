@@ -44,9 +44,10 @@ def run_components(faces, V):
     return labels[:V].cpu().numpy(), counts[:V].cpu().numpy(), tuple(stats.tolist())
 
 
-def run_filter(vert, nrm, rgb, faces, labels, face_counts, T, vcap, fcap, null_outputs=False):
+def run_filter(vert, nrm, rgb, faces, labels, face_counts, T, vcap, fcap, null_outputs=False, guard=(0, 64), spare=0):
     """tn_mesh_filter through the C ABI on sentinel-filled outputs with TAIL rows behind the capacities ->
-    (counts, vertices, normals, colors, src, faces) as numpy, ALL allocated rows"""
+    (counts, vertices, normals, colors, src, faces) as numpy, ALL allocated rows.  The workspace is
+    tn_mesh_filter_workspace_bytes + `spare` bytes with `guard` bytes of a fixed pattern before and behind it."""
     from tinynerf_amd import _lib as L
     dev = torch.device(DEV)
     V, F = vert.shape[0], faces.shape[0]
@@ -55,7 +56,8 @@ def run_filter(vert, nrm, rgb, faces, labels, face_counts, T, vcap, fcap, null_o
     d_rgb = None if rgb is None else _dev(rgb, np.uint8)
     nbytes = C.c_int64(0)
     L.call_plain("tn_mesh_filter_workspace_bytes", C.c_int64(V), C.c_int64(F), C.byref(nbytes))
-    work = torch.full((nbytes.value + 64,), 0x5A, dtype=torch.uint8, device=dev)
+    first, last = guard[0], guard[0] + nbytes.value + spare
+    work = torch.full((last + guard[1],), 0x5A, dtype=torch.uint8, device=dev)
     o_v = torch.full((vcap + TAIL, 3), SENTINEL_F, dtype=torch.float32, device=dev)
     o_n = torch.full((vcap + TAIL, 3), SENTINEL_F, dtype=torch.float32, device=dev)
     o_c = torch.full((vcap + TAIL, 3), SENTINEL_B, dtype=torch.uint8, device=dev)
@@ -64,9 +66,9 @@ def run_filter(vert, nrm, rgb, faces, labels, face_counts, T, vcap, fcap, null_o
     counts = torch.full((2,), -1, dtype=torch.int64, device=dev)
     outs = (None,) * 5 if null_outputs else (L.ptr(o_v), L.ptr(o_n), L.ptr(o_c), L.ptr(o_s), L.ptr(o_f))
     L.call("tn_mesh_filter", dev, L.ptr(d_f) if F else None, L.ptr(d_l), L.ptr(d_c), C.c_int64(T), L.ptr(d_v), L.ptr(d_n), L.ptr(d_rgb),
-           C.c_int64(V), C.c_int64(F), C.c_int64(vcap), C.c_int64(fcap), *outs, L.ptr(counts), L.ptr(work))
+           C.c_int64(V), C.c_int64(F), C.c_int64(vcap), C.c_int64(fcap), *outs, L.ptr(counts), L.ptr(work[first:]))
     torch.cuda.synchronize()
-    assert bool((work[nbytes.value:] == 0x5A).all()), "the workspace was overrun"
+    assert bool((work[:first] == 0x5A).all()) and bool((work[last:] == 0x5A).all()), "the workspace was overrun"
     return tuple(counts.tolist()), o_v.cpu().numpy(), o_n.cpu().numpy(), o_c.cpu().numpy(), o_s.cpu().numpy(), o_f.cpu().numpy()
 
 
@@ -119,6 +121,22 @@ def check_mesh(faces, V, thresholds, seed=0):
     for T in thresholds:
         check_filter(vert, nrm, rgb, faces, want, T)
     return want
+
+
+@pytest.mark.parametrize("V,F", [(1, 0), (5, 300), (300, 5), (257, 257)])
+def test_the_filter_workspace_is_what_the_size_function_says(V, F):
+    """V != F: the workgroup count is the larger one's, and the lanes past the shorter list still store ballots and counts -- inside
+    the layout: a workspace of exactly tn_mesh_filter_workspace_bytes in the middle of a larger buffer leaves the bytes around it
+    alone (`run_filter` asserts that) and gives the outputs of a generous one"""
+    faces = np.random.default_rng([V, F]).integers(0, V, (F, 3)).astype(np.int32)
+    vert, nrm, rgb = attributes(V)
+    labels, face_counts, _ = ref.components(faces, V)
+    for T in (0, 1):
+        nv, nf = ref.filter_mesh(vert, nrm, rgb, faces, T, labels, face_counts)[5]
+        tight = run_filter(vert, nrm, rgb, faces, labels, face_counts, T, nv, nf, guard=(256, 256))
+        generous = run_filter(vert, nrm, rgb, faces, labels, face_counts, T, nv, nf, guard=(256, 256), spare=4096)
+        assert tight[0] == (nv, nf), (T, tight[0])
+        assert all(np.array_equal(bits(a), bits(b)) for a, b in zip(tight[1:], generous[1:])), T
 
 
 # ------------------------------------------------------------------------------------------------------------ tiny cases

@@ -84,8 +84,9 @@ def make_case(n, pattern, seed=0):
 SENTINEL_F, SENTINEL_B, SENTINEL_I = -7.25, 0xA5, -12345
 
 
-def run(case, box=BOX, bg=BG, min_opacity=MIN_OPACITY, capacity=None, null_outputs=False):
-    """tn_points_compact through the C ABI on sentinel-filled outputs -> (count, points, colors, src) as numpy, ALL `capacity` rows"""
+def run(case, box=BOX, bg=BG, min_opacity=MIN_OPACITY, capacity=None, null_outputs=False, guard=(0, 64), spare=0):
+    """tn_points_compact through the C ABI on sentinel-filled outputs -> (count, points, colors, src) as numpy, ALL `capacity` rows.
+    The workspace is tn_points_workspace_bytes + `spare` bytes with `guard` bytes of a fixed pattern before and behind it."""
     from tinynerf_amd import _lib as L
     dev = torch.device(DEV)
     t = {k: torch.from_numpy(np.ascontiguousarray(case[k])).to(dev) for k in ("rays_o", "rays_d", "rgb", "opacity", "depth")}
@@ -95,16 +96,17 @@ def run(case, box=BOX, bg=BG, min_opacity=MIN_OPACITY, capacity=None, null_outpu
     box_t = None if box is None else torch.from_numpy(np.float32(box)).to(dev)
     nbytes = C.c_int64(0)
     L.call_plain("tn_points_workspace_bytes", C.c_int64(n), C.byref(nbytes))
-    work = torch.full((nbytes.value + 64,), 0x5A, dtype=torch.uint8, device=dev)              # 64 guard bytes behind the workspace
+    first, last = guard[0], guard[0] + nbytes.value + spare
+    work = torch.full((last + guard[1],), 0x5A, dtype=torch.uint8, device=dev)
     points = torch.full((cap, 3), SENTINEL_F, dtype=torch.float32, device=dev)
     colors = torch.full((cap, 3), SENTINEL_B, dtype=torch.uint8, device=dev)
     src = torch.full((cap,), SENTINEL_I, dtype=torch.int32, device=dev)
     count = torch.full((1,), -1, dtype=torch.int64, device=dev)
     outs = (None, None, None) if null_outputs else (L.ptr(points), L.ptr(colors), L.ptr(src))
     L.call("tn_points_compact", dev, L.ptr(t["rays_o"]), L.ptr(t["rays_d"]), L.ptr(t["rgb"]), L.ptr(t["opacity"]), L.ptr(t["depth"]),
-           L.ptr(bg_t), L.ptr(box_t), C.c_float(min_opacity), C.c_int64(n), C.c_int64(cap), *outs, L.ptr(count), L.ptr(work))
+           L.ptr(bg_t), L.ptr(box_t), C.c_float(min_opacity), C.c_int64(n), C.c_int64(cap), *outs, L.ptr(count), L.ptr(work[first:]))
     torch.cuda.synchronize()
-    assert bool((work[nbytes.value:] == 0x5A).all()), "the workspace was overrun"
+    assert bool((work[:first] == 0x5A).all()) and bool((work[last:] == 0x5A).all()), "the workspace was overrun"
     return int(count.item()), points.cpu().numpy(), colors.cpu().numpy(), src.cpu().numpy()
 
 
@@ -133,6 +135,18 @@ def test_selection_order_and_values(n):
         m, err, levels = check_against_yardstick(case, run(case), tag=(n, pattern))
         assert m == int(case["want"].sum())
         print(f"n {n} {pattern}: kept {m}, worst point error {err:.2f} ulp, colour bytes off by one level: {levels}")
+
+
+@pytest.mark.parametrize("n", [1, 63, 65, 257])
+def test_the_workspace_is_what_the_size_function_says(n):
+    """a wave that starts past n and a last workgroup with one live lane store their ballots and counts inside the layout: a
+    workspace of exactly tn_points_workspace_bytes in the middle of a larger buffer leaves the bytes around it alone (`run`
+    asserts that) and gives the outputs of a generous one"""
+    for pattern in ("all", "last", "random50"):
+        case = make_case(n, pattern)
+        tight, generous = run(case, guard=(256, 256)), run(case, guard=(256, 256), spare=4096)
+        assert tight[0] == generous[0] == int(case["want"].sum()), (n, pattern)
+        assert all(np.array_equal(a, b) for a, b in zip(tight[1:], generous[1:])), (n, pattern)
 
 
 def _dyadic_batch(n=300):

@@ -84,11 +84,14 @@ def test_library_exports_and_the_guide_names_the_points_entry_points(lib):
     assert build.SOURCES["points.hip"] == build.SOURCES["cameras.hip"]
 
 
+WORKSPACE_N = list(range(0, 1100)) + [4099, 65536 + 257, 640000, 2 ** 20 + 13, 2 ** 31 - 1]
+
+
 def test_workspace_bytes(lib):
     q, i64 = lib.tn_points_workspace_bytes, ctypes.c_int64
     out = i64(-1)
     prev = 0
-    for n in list(range(0, 1100)) + [4099, 65536 + 257, 640000, 2 ** 20 + 13, 2 ** 31 - 1]:
+    for n in WORKSPACE_N:
         assert q(i64(n), ctypes.byref(out)) == 0
         assert out.value >= 8 * -(-n // 64) + 8 * -(-n // 256) and out.value >= prev and out.value % 8 == 0
         prev = out.value
@@ -97,6 +100,14 @@ def test_workspace_bytes(lib):
     assert q(i64(8), None) == -1 and b"tn_points_workspace_bytes" in lib.tn_last_error_string()
     assert q(i64(-1), ctypes.byref(out)) == -2
     assert q(i64(2 ** 31), ctypes.byref(out)) == -2
+
+
+def test_workspace_bytes_are_the_shared_layout(lib):
+    """per workgroup of 256 rays 4 waves x 1 ballot and 1 count of 8 B each: the layout the mesh and filter workspaces start with"""
+    out = ctypes.c_int64(-1)
+    for n in WORKSPACE_N:
+        assert lib.tn_points_workspace_bytes(ctypes.c_int64(n), ctypes.byref(out)) == 0
+        assert out.value == 40 * -(-n // 256), n
 
 
 def test_compact_rejects_bad_arguments_before_launching(lib):

@@ -11,22 +11,23 @@
 //     counter-clockwise seen from +a, reversed when the lower node is outside; triangles (q0,q1,q2), (q0,q2,q3)
 // The k-th active cell in cell order writes vertex row k, the m-th quad in (cell, axis) order face rows 2m and 2m + 1.
 //
-// Four launches on the caller's stream, one lane per cell, no atomics -- the same bytes on every call:
+// Four launches on the caller's stream, one lane per cell, no atomics -- the same bytes on every call (the pattern's pieces:
+// compact_device.h; the grid's: grid_device.h):
 //   mesh_mark_kernel      every wave writes 4 ballots (active, quad on axis 0 / 1 / 2), every workgroup of 256 its two counts
-//   mesh_scan_kernel      one workgroup per count column turns it into exclusive offsets (scan_device.h) and writes its entry of counts[2]
+//   mesh_scan_kernel      one workgroup per count column turns it into exclusive offsets and writes its entry of counts[2]
 //   mesh_vertex_kernel    rank = workgroup offset + active cells of the earlier waves + set ballot bits below the lane; stores the
 //                         cell's vertex id (-1: inactive) in the map and, if rank < vertex_capacity, the vertex and normal rows
 //   mesh_face_kernel      quad rank likewise over the three quad ballots; reads 4 ids from the map, stores 6 indices
 // Workspace (tn_mesh_workspace_bytes), G = ceil(cells / 256): G x 4 waves x 4 ballots of 8 B, 2 x G counts of 8 B, cells ids of 4 B.
 #include <cmath>
-#include "tn_common.h"
-#include "scan_device.h"
+#include "compact_device.h"
+#include "grid_device.h"
 
 namespace {
 
-constexpr int THREADS = 256;                 // mark / vertices / faces: 4 waves, one pair of workspace slots per workgroup
-constexpr int WAVES = THREADS / TN_WAVE;
+constexpr int THREADS = tn::COMPACT_THREADS; // mark / vertices / faces: 4 waves, one pair of workspace slots per workgroup
 constexpr int BALLOTS = 4;                   // per wave: active, quad on axis 0, 1, 2
+constexpr int COLUMNS = 2;                   // counts per workgroup: vertices, quads (the three quad ballots summed)
 constexpr int SCAN_THREADS = 1024;           // scan: workgroup counts per trip of its loop
 
 struct MeshGrid {
@@ -37,60 +38,32 @@ struct MeshGrid {
     int64_t cells;
 };
 
-// cell c -> its index on every axis and its lowest corner's node
-__device__ __forceinline__ void cell_of(const MeshGrid &g, uint32_t c, int idx[3], int64_t &node)
-{
-    const uint32_t row = c / (uint32_t)g.nx, k = row / (uint32_t)g.ny;
-    idx[0] = (int)(c - row * (uint32_t)g.nx);
-    idx[1] = (int)(row - k * (uint32_t)g.ny);
-    idx[2] = (int)k;
-    node = idx[0] + ((int64_t)g.nx + 1) * (idx[1] + ((int64_t)g.ny + 1) * idx[2]);
-}
-
 // corner d = dx + 2 dy + 4 dz of the cell whose lowest corner is `node`; bit d of the result: inside
 __device__ __forceinline__ uint32_t load_corners(const MeshGrid &g, int64_t node, float v[8])
 {
-    const int64_t sy = (int64_t)g.nx + 1, sz = sy * ((int64_t)g.ny + 1);
     uint32_t in = 0;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) {
-        v[d] = g.values[node + (d & 1) + ((d >> 1) & 1) * sy + (d >> 2) * sz];
+    tn::for_corners(g.nx, g.ny, node, [&](int d, int64_t n) {
+        v[d] = g.values[n];
         in |= (v[d] >= g.level ? 1u : 0u) << d;
-    }
+    });
     return in;
 }
 
 __global__ __launch_bounds__(THREADS) void mesh_mark_kernel(MeshGrid g, uint64_t *__restrict__ ballots, int64_t *__restrict__ group, int64_t n_groups)
 {
-    __shared__ int wave_vertices[WAVES], wave_quads[WAVES];
-    const int tid = (int)threadIdx.x, wave = tid / TN_WAVE;
-    const int64_t c = (int64_t)blockIdx.x * THREADS + tid;
-    bool active = false, quad[3] = {false, false, false};
+    const int64_t c = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    bool bit[BALLOTS] = {false, false, false, false};            // active, a quad on axis 0 / 1 / 2
     if (c < g.cells) {                                           // (lanes past the last cell stay in the ballots with 0 bits)
         int idx[3];
         int64_t node;
         float v[8];
-        cell_of(g, (uint32_t)c, idx, node);
+        tn::cell_of(g.nx, g.ny, (uint32_t)c, idx, node);
         const uint32_t in = load_corners(g, node, v);
-        active = in != 0u && in != 255u;
+        bit[0] = in != 0u && in != 255u;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) quad[a] = ((in ^ (in >> (1 << a))) & 1u) && idx[(a + 1) % 3] >= 1 && idx[(a + 2) % 3] >= 1;
+        for (int a = 0; a < 3; ++a) bit[1 + a] = ((in ^ (in >> (1 << a))) & 1u) && idx[(a + 1) % 3] >= 1 && idx[(a + 2) % 3] >= 1;
     }
-    const uint64_t m = __ballot(active), q0 = __ballot(quad[0]), q1 = __ballot(quad[1]), q2 = __ballot(quad[2]);
-    if (tn::lane_id() == 0) {
-        uint64_t *b = ballots + ((int64_t)blockIdx.x * WAVES + wave) * BALLOTS;
-        b[0] = m, b[1] = q0, b[2] = q1, b[3] = q2;
-        wave_vertices[wave] = __popcll(m);
-        wave_quads[wave] = __popcll(q0) + __popcll(q1) + __popcll(q2);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int sv = 0, sq = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) sv += wave_vertices[w], sq += wave_quads[w];
-        group[blockIdx.x] = sv;
-        group[n_groups + blockIdx.x] = sq;
-    }
+    tn::compact_mark<BALLOTS, COLUMNS>(bit, ballots, group, n_groups);
 }
 
 // workgroup 0 / 1 takes the vertex / quad column of group: counts in, exclusive offsets out; counts[0] = vertices, counts[1] = triangles
@@ -105,23 +78,15 @@ __global__ __launch_bounds__(THREADS) void mesh_vertex_kernel(MeshGrid g, const 
                                                               int64_t capacity, float *__restrict__ vertices, float *__restrict__ normals,
                                                               int32_t *__restrict__ map)
 {
-    const int tid = (int)threadIdx.x, wave = tid / TN_WAVE;
-    const int64_t c = (int64_t)blockIdx.x * THREADS + tid;
+    const int64_t c = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (c >= g.cells) return;
-    const uint64_t *b = ballots + (int64_t)blockIdx.x * WAVES * BALLOTS;
-    const uint64_t m = b[wave * BALLOTS];
-    if (!((m >> tn::lane_id()) & 1)) {
-        map[c] = -1;
-        return;
-    }
-    int64_t rank = group[blockIdx.x] + tn::rank_below(m);
-    for (int w = 0; w < wave; ++w) rank += __popcll(b[w * BALLOTS]);
-    map[c] = (int32_t)rank;                                      // (whatever the capacity: the faces name every vertex)
-    if (rank >= capacity) return;
+    const int64_t rank = tn::compact_rank<BALLOTS>(ballots, group, 0);
+    map[c] = (int32_t)rank;                                      // (-1: inactive; whatever the capacity: the faces name every vertex)
+    if (rank < 0 || rank >= capacity) return;
     int idx[3];
     int64_t node;
     float v[8];
-    cell_of(g, (uint32_t)c, idx, node);
+    tn::cell_of(g.nx, g.ny, (uint32_t)c, idx, node);
     const uint32_t in = load_corners(g, node, v);
     float sum[3] = {0.0f, 0.0f, 0.0f};
     int crossed = 0;
@@ -170,22 +135,19 @@ __global__ __launch_bounds__(THREADS) void mesh_face_kernel(MeshGrid g, const ui
                                                             int64_t n_groups, int64_t capacity, const int32_t *__restrict__ map,
                                                             int32_t *__restrict__ faces)
 {
-    const int tid = (int)threadIdx.x, wave = tid / TN_WAVE, lane = tn::lane_id();
-    const int64_t c = (int64_t)blockIdx.x * THREADS + tid;
+    const int64_t c = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (c >= g.cells) return;
-    const uint64_t *b = ballots + (int64_t)blockIdx.x * WAVES * BALLOTS;
-    const uint64_t q[3] = {b[wave * BALLOTS + 1], b[wave * BALLOTS + 2], b[wave * BALLOTS + 3]};
-    if (!(((q[0] | q[1] | q[2]) >> lane) & 1)) return;
-    int64_t rank = group[n_groups + blockIdx.x] + tn::rank_below(q[0]) + tn::rank_below(q[1]) + tn::rank_below(q[2]);
-    for (int w = 0; w < wave; ++w) rank += __popcll(b[w * BALLOTS + 1]) + __popcll(b[w * BALLOTS + 2]) + __popcll(b[w * BALLOTS + 3]);
+    uint32_t quads;                                              // bit a: this cell has a quad on axis a
+    int64_t rank = tn::compact_rank<BALLOTS, 3>(ballots, group + n_groups, 1, &quads);
+    if (rank < 0) return;
     int idx[3];
     int64_t node;
-    cell_of(g, (uint32_t)c, idx, node);
+    tn::cell_of(g.nx, g.ny, (uint32_t)c, idx, node);
     const bool lower_inside = g.values[node] >= g.level;
     const int64_t stride[3] = {1, g.nx, (int64_t)g.nx * g.ny};     // of the cell index (a quad's axes b, c have idx >= 1: no wrap)
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        if (!((q[a] >> lane) & 1)) continue;
+        if (!((quads >> a) & 1)) continue;
         const int64_t sb = stride[(a + 1) % 3], sc = stride[(a + 2) % 3];
         int32_t q0 = map[c - sb - sc], q1 = map[c - sc], q2 = map[c], q3 = map[c - sb];
         if (!lower_inside) {
@@ -204,24 +166,10 @@ __global__ __launch_bounds__(THREADS) void grid_nodes_kernel(MeshGrid g, int64_t
 {
     const int64_t t = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (t >= n) return;
-    const int64_t m = first + t, sx = (int64_t)g.nx + 1, sy = (int64_t)g.ny + 1;
-    const int64_t row = m / sx, k = row / sy;
-    const int64_t idx[3] = {m - row * sx, row - k * sy, k};
+    float x[3];
+    tn::node_position<int64_t>(first + t, (int64_t)g.nx + 1, (int64_t)g.ny + 1, g.lo, g.h, x);      // (64-bit: a grid's nodes can pass 2^31)
 #pragma unroll
-    for (int a = 0; a < 3; ++a) out[3 * t + a] = fmaf((float)idx[a], g.h[a], g.lo[a]);
-}
-
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// the number of cells of dims, -1 unless every dim is >= 0 and the number is below 2^31
-int64_t cell_count(int64_t nx, int64_t ny, int64_t nz)
-{
-    const int64_t limit = (int64_t)1 << 31;
-    if (nx < 0 || ny < 0 || nz < 0 || nx >= limit || ny >= limit || nz >= limit) return -1;
-    if (nx == 0 || ny == 0 || nz == 0) return 0;
-    const int64_t xy = nx * ny;
-    if (xy >= limit || xy * nz >= limit) return -1;
-    return xy * nz;
+    for (int a = 0; a < 3; ++a) out[3 * t + a] = x[a];
 }
 
 MeshGrid grid_of(const float *values, const int32_t *dims, const float *lo, const float *h, float level, int64_t cells)
@@ -240,25 +188,25 @@ MeshGrid grid_of(const float *values, const int32_t *dims, const float *lo, cons
 extern "C" int tn_mesh_workspace_bytes(int32_t nx, int32_t ny, int32_t nz, int64_t *bytes)
 {
     TN_REQUIRE(bytes, TN_E_NULL, "tn_mesh_workspace_bytes: null pointer");
-    const int64_t cells = cell_count(nx, ny, nz);
+    const int32_t dims[3] = {nx, ny, nz};
+    const int64_t cells = tn::grid_count(dims, false);
     TN_REQUIRE(cells >= 0, TN_E_SIZE, "tn_mesh_workspace_bytes: dims must be >= 0 with fewer than 2^31 cells");
-    const int64_t groups = ceil_div(cells, THREADS);
-    *bytes = 8 * (WAVES * BALLOTS + 2) * groups + 8 * ceil_div(cells, 2);
+    *bytes = tn::compact_bytes<BALLOTS, COLUMNS>(tn::ceil_div(cells, THREADS)) + 8 * tn::ceil_div(cells, 2);
     return TN_OK;
 }
 
 extern "C" int tn_grid_nodes(const float *lo, const float *h, const int32_t *dims, int64_t first, int64_t n, float *out, void *stream)
 {
     TN_REQUIRE(lo && h && dims, TN_E_NULL, "tn_grid_nodes: null pointer (lo, h, dims)");
-    const int64_t cells = cell_count(dims[0], dims[1], dims[2]);
+    const int64_t cells = tn::grid_count(dims, false);
     TN_REQUIRE(cells >= 0, TN_E_SIZE, "tn_grid_nodes: dims must be >= 0 with fewer than 2^31 cells");
     const int64_t nodes = ((int64_t)dims[0] + 1) * ((int64_t)dims[1] + 1) * ((int64_t)dims[2] + 1);      // (< 2^34, or 2^62 with an empty axis)
     TN_REQUIRE(first >= 0 && n >= 0 && n <= nodes && first <= nodes - n, TN_E_SIZE, "tn_grid_nodes: first .. first + n must lie inside the grid's nodes");
     if (n == 0) return TN_OK;
     TN_REQUIRE(out, TN_E_NULL, "tn_grid_nodes: null pointer (out)");
-    TN_REQUIRE(ceil_div(n, THREADS) < ((int64_t)1 << 31), TN_E_SIZE, "tn_grid_nodes: n must be below 2^39");
+    TN_REQUIRE(tn::ceil_div(n, THREADS) < ((int64_t)1 << 31), TN_E_SIZE, "tn_grid_nodes: n must be below 2^39");
     const MeshGrid g = grid_of(nullptr, dims, lo, h, 0.0f, cells);
-    grid_nodes_kernel<<<dim3((unsigned)ceil_div(n, THREADS)), dim3(THREADS), 0, (hipStream_t)stream>>>(g, first, n, out);
+    grid_nodes_kernel<<<dim3((unsigned)tn::ceil_div(n, THREADS)), dim3(THREADS), 0, (hipStream_t)stream>>>(g, first, n, out);
     return tn::check_launch("grid_nodes_kernel");
 }
 
@@ -267,7 +215,7 @@ extern "C" int tn_mesh_extract(const float *values, const int32_t *dims, const f
                                void *stream)
 {
     TN_REQUIRE(dims && lo && h, TN_E_NULL, "tn_mesh_extract: null pointer (dims, lo, h)");
-    const int64_t cells = cell_count(dims[0], dims[1], dims[2]);
+    const int64_t cells = tn::grid_count(dims, false);
     TN_REQUIRE(cells >= 0, TN_E_SIZE, "tn_mesh_extract: dims must be >= 0 with fewer than 2^31 cells (vertex ids are int32)");
     TN_REQUIRE(vertex_capacity >= 0 && face_capacity >= 0, TN_E_SIZE, "tn_mesh_extract: negative capacity");
     TN_REQUIRE(std::isfinite(level), TN_E_CONFIG, "tn_mesh_extract: level must be finite");
@@ -275,25 +223,18 @@ extern "C" int tn_mesh_extract(const float *values, const int32_t *dims, const f
     TN_REQUIRE(vertex_capacity == 0 || vertices, TN_E_NULL, "tn_mesh_extract: null output pointer (vertices) with vertex_capacity > 0");
     TN_REQUIRE(face_capacity == 0 || faces, TN_E_NULL, "tn_mesh_extract: null output pointer (faces) with face_capacity > 0");
     hipStream_t s = (hipStream_t)stream;
-    if (cells == 0) {
-        hipError_t e = hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s);
-        if (e != hipSuccess) {
-            tn::set_error("tn_mesh_extract: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        return TN_OK;
-    }
+    if (cells == 0) return tn::zero_bytes(counts, 2 * sizeof(int64_t), s, "tn_mesh_extract");
     TN_REQUIRE(values && workspace, TN_E_NULL, "tn_mesh_extract: null pointer (values, workspace)");
     TN_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)counts & 7) == 0, TN_E_ALIGN, "tn_mesh_extract: workspace and counts must be 8-byte aligned");
     const MeshGrid g = grid_of(values, dims, lo, h, level, cells);
-    const int64_t n_groups = ceil_div(cells, THREADS);
+    const int64_t n_groups = tn::ceil_div(cells, THREADS);
     uint64_t *ballots = (uint64_t *)workspace;
-    int64_t *group = (int64_t *)workspace + WAVES * BALLOTS * n_groups;
-    int32_t *map = (int32_t *)(group + 2 * n_groups);
+    int64_t *group = tn::compact_group<BALLOTS>(workspace, n_groups);
+    int32_t *map = (int32_t *)(group + COLUMNS * n_groups);
     mesh_mark_kernel<<<dim3((unsigned)n_groups), dim3(THREADS), 0, s>>>(g, ballots, group, n_groups);
     int rc = tn::check_launch("mesh_mark_kernel");
     if (rc != TN_OK) return rc;
-    mesh_scan_kernel<<<dim3(2), dim3(SCAN_THREADS), 0, s>>>(group, n_groups, counts);
+    mesh_scan_kernel<<<dim3(COLUMNS), dim3(SCAN_THREADS), 0, s>>>(group, n_groups, counts);
     rc = tn::check_launch("mesh_scan_kernel");
     if (rc != TN_OK || (vertex_capacity == 0 && face_capacity == 0)) return rc;
     mesh_vertex_kernel<<<dim3((unsigned)n_groups), dim3(THREADS), 0, s>>>(g, ballots, group, vertex_capacity, vertices, normals, map);

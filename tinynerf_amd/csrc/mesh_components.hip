@@ -22,21 +22,20 @@
 // read and written with relaxed agent-scope atomics while the hook kernel runs (a plain load may be served a stale line by the XCD's
 // L2 for ever; a stale parent is still an ancestor, but a retry loop must see the CAS that beat it).
 //
-// tn_mesh_filter -- four launches, no atomics, the ballot / scan / ranked-store pattern of mesh.hip:
+// tn_mesh_filter -- four launches, no atomics, the ballot / scan / ranked-store pattern of mesh.hip (compact_device.h):
 //   filter_mark_kernel    lane i takes vertex i and face i: every wave writes 2 ballots (vertex kept, face kept), every workgroup 2 counts
-//   filter_scan_kernel    one workgroup per count column: exclusive offsets (scan_device.h) and its entry of counts[2]
+//   filter_scan_kernel    one workgroup per count column: exclusive offsets and its entry of counts[2]
 //   filter_vertex_kernel  rank = workgroup offset + kept vertices of the earlier waves + set ballot bits below the lane; stores the
 //                         old -> new map (-1: dropped) and, if rank < vertex_capacity, the attribute rows and src
 //   filter_face_kernel    rank likewise over the face ballots; stores the three indices renumbered through the map
 // Workspace (tn_mesh_filter_workspace_bytes), G = ceil(max(V, F) / 256): G x 4 waves x 2 ballots of 8 B, 2 x G counts of 8 B, V ids of 4 B.
-#include "tn_common.h"
-#include "scan_device.h"
+#include "compact_device.h"
 
 namespace {
 
-constexpr int THREADS = 256;                 // every kernel but the two single-workgroup ones: 4 waves
+constexpr int THREADS = tn::COMPACT_THREADS; // every kernel but the two single-workgroup ones: 4 waves
 constexpr int WAVES = THREADS / TN_WAVE;
-constexpr int BALLOTS = 2;                   // per wave: vertex kept, face kept
+constexpr int BALLOTS = 2;                   // per wave: vertex kept, face kept -- and a count column for each
 constexpr int SCAN_THREADS = 1024;           // scan / reduce: workgroup values per trip of the loop
 
 __device__ __forceinline__ int32_t load_label(const int32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -170,30 +169,13 @@ __device__ __forceinline__ bool vertex_kept(const FilterMesh &m, int32_t v)
 
 __global__ __launch_bounds__(THREADS) void filter_mark_kernel(FilterMesh m, uint64_t *__restrict__ ballots, int64_t *__restrict__ group, int64_t n_groups)
 {
-    __shared__ int wave_vertices[WAVES], wave_faces[WAVES];
-    const int tid = (int)threadIdx.x, wave = tid / TN_WAVE;
-    const int64_t i = (int64_t)blockIdx.x * THREADS + tid;
-    const bool keep_vertex = i < m.n_vertices && vertex_kept(m, (int32_t)i);
-    bool keep_face = false;
+    const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    bool keep[BALLOTS] = {i < m.n_vertices && vertex_kept(m, (int32_t)i), false};      // vertex i, face i
     if (i < m.n_faces) {                                           // (lanes past the last vertex / face stay in the ballots with 0 bits)
         int32_t v[3];
-        keep_face = load_face(m.faces, i, (int32_t)m.n_vertices, v) && vertex_kept(m, v[0]);
+        keep[1] = load_face(m.faces, i, (int32_t)m.n_vertices, v) && vertex_kept(m, v[0]);
     }
-    const uint64_t bv = __ballot(keep_vertex), bf = __ballot(keep_face);
-    if (tn::lane_id() == 0) {
-        uint64_t *b = ballots + ((int64_t)blockIdx.x * WAVES + wave) * BALLOTS;
-        b[0] = bv, b[1] = bf;
-        wave_vertices[wave] = __popcll(bv);
-        wave_faces[wave] = __popcll(bf);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int sv = 0, sf = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) sv += wave_vertices[w], sf += wave_faces[w];
-        group[blockIdx.x] = sv;
-        group[n_groups + blockIdx.x] = sf;
-    }
+    tn::compact_mark<BALLOTS, BALLOTS>(keep, ballots, group, n_groups);
 }
 
 // workgroup 0 / 1 takes the vertex / face column of group: counts in, exclusive offsets out; counts[0] = kept vertices, counts[1] = kept faces
@@ -201,18 +183,6 @@ __global__ __launch_bounds__(SCAN_THREADS) void filter_scan_kernel(int64_t *__re
 {
     const int64_t column = blockIdx.x;
     tn::scan_group_counts<SCAN_THREADS>(group + column * n_groups, n_groups, counts + column);
-}
-
-// the rank of this lane's set bit in ballot column `which` of its workgroup, -1 when the bit is clear
-__device__ __forceinline__ int64_t ranked(const uint64_t *__restrict__ ballots, const int64_t *__restrict__ offsets, int which)
-{
-    const int wave = (int)threadIdx.x / TN_WAVE;
-    const uint64_t *b = ballots + (int64_t)blockIdx.x * WAVES * BALLOTS + which;
-    const uint64_t mine = b[wave * BALLOTS];
-    if (!((mine >> tn::lane_id()) & 1)) return -1;
-    int64_t rank = offsets[blockIdx.x] + tn::rank_below(mine);
-    for (int w = 0; w < wave; ++w) rank += __popcll(b[w * BALLOTS]);
-    return rank;
 }
 
 __global__ __launch_bounds__(THREADS) void filter_vertex_kernel(int64_t n_vertices, const uint64_t *__restrict__ ballots, const int64_t *__restrict__ group,
@@ -223,7 +193,7 @@ __global__ __launch_bounds__(THREADS) void filter_vertex_kernel(int64_t n_vertic
 {
     const int64_t v = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (v >= n_vertices) return;
-    const int64_t rank = ranked(ballots, group, 0);
+    const int64_t rank = tn::compact_rank<BALLOTS>(ballots, group, 0);
     map[v] = (int32_t)rank;                                        // (whatever the capacity: the kept faces name every kept vertex)
     if (rank < 0 || rank >= capacity) return;
     src[rank] = (int32_t)v;
@@ -241,28 +211,16 @@ __global__ __launch_bounds__(THREADS) void filter_face_kernel(const int32_t *__r
 {
     const int64_t f = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (f >= n_faces) return;
-    const int64_t rank = ranked(ballots, group + n_groups, 1);
+    const int64_t rank = tn::compact_rank<BALLOTS>(ballots, group + n_groups, 1);
     if (rank < 0 || rank >= capacity) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) out_faces[3 * rank + k] = map[faces[3 * f + k]];      // (a kept face is valid: its ids lie in [0, V))
 }
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 bool sizes_ok(int64_t n_vertices, int64_t n_faces)
 {
     const int64_t limit = (int64_t)1 << 31;
     return n_vertices >= 0 && n_faces >= 0 && n_vertices < limit && n_faces < limit;
-}
-
-int zero_words(int64_t *p, int n, hipStream_t s, const char *who)
-{
-    hipError_t e = hipMemsetAsync(p, 0, n * sizeof(int64_t), s);
-    if (e != hipSuccess) {
-        tn::set_error("%s: %s", who, hipGetErrorString(e));
-        return (int)e;
-    }
-    return TN_OK;
 }
 
 }  // namespace
@@ -271,7 +229,7 @@ extern "C" int tn_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_
 {
     TN_REQUIRE(bytes, TN_E_NULL, "tn_mesh_components_workspace_bytes: null pointer");
     TN_REQUIRE(sizes_ok(n_vertices, n_faces), TN_E_SIZE, "tn_mesh_components_workspace_bytes: sizes must be >= 0 and below 2^31");
-    *bytes = 3 * 8 * ceil_div(n_vertices, THREADS);
+    *bytes = 3 * 8 * tn::ceil_div(n_vertices, THREADS);
     return TN_OK;
 }
 
@@ -281,11 +239,11 @@ extern "C" int tn_mesh_components(const int32_t *faces, int64_t n_vertices, int6
     TN_REQUIRE(sizes_ok(n_vertices, n_faces), TN_E_SIZE, "tn_mesh_components: n_vertices and n_faces must be >= 0 and below 2^31 (vertex ids are int32)");
     TN_REQUIRE(stats, TN_E_NULL, "tn_mesh_components: null pointer (stats)");
     hipStream_t s = (hipStream_t)stream;
-    if (n_vertices == 0) return zero_words(stats, 3, s, "tn_mesh_components");
+    if (n_vertices == 0) return tn::zero_bytes(stats, 3 * sizeof(int64_t), s, "tn_mesh_components");
     TN_REQUIRE(labels && face_counts && workspace, TN_E_NULL, "tn_mesh_components: null pointer (labels, face_counts, workspace)");
     TN_REQUIRE(n_faces == 0 || faces, TN_E_NULL, "tn_mesh_components: null pointer (faces) with n_faces > 0");
     TN_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)stats & 7) == 0, TN_E_ALIGN, "tn_mesh_components: workspace and stats must be 8-byte aligned");
-    const int64_t vertex_groups = ceil_div(n_vertices, THREADS), face_groups = ceil_div(n_faces, THREADS);
+    const int64_t vertex_groups = tn::ceil_div(n_vertices, THREADS), face_groups = tn::ceil_div(n_faces, THREADS);
     int64_t *partial = (int64_t *)workspace;
     components_init_kernel<<<dim3((unsigned)vertex_groups), dim3(THREADS), 0, s>>>(labels, face_counts, n_vertices);
     int rc = tn::check_launch("components_init_kernel");
@@ -312,8 +270,7 @@ extern "C" int tn_mesh_filter_workspace_bytes(int64_t n_vertices, int64_t n_face
 {
     TN_REQUIRE(bytes, TN_E_NULL, "tn_mesh_filter_workspace_bytes: null pointer");
     TN_REQUIRE(sizes_ok(n_vertices, n_faces), TN_E_SIZE, "tn_mesh_filter_workspace_bytes: sizes must be >= 0 and below 2^31");
-    const int64_t groups = ceil_div(n_vertices > n_faces ? n_vertices : n_faces, THREADS);
-    *bytes = 8 * (WAVES * BALLOTS + 2) * groups + 8 * ceil_div(n_vertices, 2);
+    *bytes = tn::compact_bytes<BALLOTS, BALLOTS>(tn::ceil_div(n_vertices > n_faces ? n_vertices : n_faces, THREADS)) + 8 * tn::ceil_div(n_vertices, 2);
     return TN_OK;
 }
 
@@ -327,7 +284,7 @@ extern "C" int tn_mesh_filter(const int32_t *faces, const int32_t *labels, const
     TN_REQUIRE(threshold >= 0, TN_E_CONFIG, "tn_mesh_filter: threshold must be >= 0");
     TN_REQUIRE(counts, TN_E_NULL, "tn_mesh_filter: null pointer (counts)");
     hipStream_t s = (hipStream_t)stream;
-    if (n_vertices == 0) return zero_words(counts, 2, s, "tn_mesh_filter");
+    if (n_vertices == 0) return tn::zero_bytes(counts, 2 * sizeof(int64_t), s, "tn_mesh_filter");
     TN_REQUIRE(labels && face_counts && workspace, TN_E_NULL, "tn_mesh_filter: null pointer (labels, face_counts, workspace)");
     TN_REQUIRE(n_faces == 0 || faces, TN_E_NULL, "tn_mesh_filter: null pointer (faces) with n_faces > 0");
     TN_REQUIRE(vertex_capacity == 0 || (vertices && out_vertices && src), TN_E_NULL,
@@ -336,18 +293,18 @@ extern "C" int tn_mesh_filter(const int32_t *faces, const int32_t *labels, const
                "tn_mesh_filter: null output pointer (out_normals, out_colors) for an input that is given, with vertex_capacity > 0");
     TN_REQUIRE(face_capacity == 0 || out_faces, TN_E_NULL, "tn_mesh_filter: null output pointer (out_faces) with face_capacity > 0");
     TN_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)counts & 7) == 0, TN_E_ALIGN, "tn_mesh_filter: workspace and counts must be 8-byte aligned");
-    const int64_t vertex_groups = ceil_div(n_vertices, THREADS), face_groups = ceil_div(n_faces, THREADS);
+    const int64_t vertex_groups = tn::ceil_div(n_vertices, THREADS), face_groups = tn::ceil_div(n_faces, THREADS);
     const int64_t n_groups = vertex_groups > face_groups ? vertex_groups : face_groups;
     uint64_t *ballots = (uint64_t *)workspace;
-    int64_t *group = (int64_t *)workspace + WAVES * BALLOTS * n_groups;
-    int32_t *map = (int32_t *)(group + 2 * n_groups);
+    int64_t *group = tn::compact_group<BALLOTS>(workspace, n_groups);
+    int32_t *map = (int32_t *)(group + BALLOTS * n_groups);
     FilterMesh m;
     m.faces = faces, m.labels = labels, m.face_counts = face_counts;
     m.n_vertices = n_vertices, m.n_faces = n_faces, m.threshold = threshold;
     filter_mark_kernel<<<dim3((unsigned)n_groups), dim3(THREADS), 0, s>>>(m, ballots, group, n_groups);
     int rc = tn::check_launch("filter_mark_kernel");
     if (rc != TN_OK) return rc;
-    filter_scan_kernel<<<dim3(2), dim3(SCAN_THREADS), 0, s>>>(group, n_groups, counts);
+    filter_scan_kernel<<<dim3(BALLOTS), dim3(SCAN_THREADS), 0, s>>>(group, n_groups, counts);
     rc = tn::check_launch("filter_scan_kernel");
     if (rc != TN_OK || (vertex_capacity == 0 && face_capacity == 0)) return rc;
     filter_vertex_kernel<<<dim3((unsigned)vertex_groups), dim3(THREADS), 0, s>>>(n_vertices, ballots, group, vertex_capacity, vertices, normals, colors,

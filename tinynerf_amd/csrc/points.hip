@@ -8,18 +8,17 @@
 //   byte = (uint8_t)fmaf(c, 255, 0.5)
 // The k-th kept ray, in ray order, writes row k of points / colors / src while k < capacity; *count = the number of kept rays.
 //
-// Three launches on the caller's stream, one lane per ray, no atomics -- the same bytes on every call:
+// Three launches on the caller's stream, one lane per ray, no atomics -- the same bytes on every call (the pattern's pieces: compact_device.h):
 //   points_mark_kernel    evaluates the predicate; every wave writes its 64-bit ballot, every workgroup of 256 its number of kept rays
 //   points_scan_kernel    ONE workgroup turns the workgroup counts into exclusive offsets, 1024 at a time with a carry, and writes *count
 //   points_write_kernel   rank = workgroup offset + kept rays of the workgroup's earlier waves + set ballot bits below the lane; a kept
 //                         lane recomputes its point and colour and stores row `rank` (12 + 3 + 4 B) if rank < capacity
-// Workspace: ceil(n / 64) ballots of 8 B, then ceil(n / 256) workgroup slots of 8 B (tn_points_workspace_bytes).
-#include "tn_common.h"
+// Workspace, G = ceil(n / 256): G x 4 waves x 1 ballot of 8 B, then G workgroup counts of 8 B (tn_points_workspace_bytes).
+#include "compact_device.h"
 
 namespace {
 
-constexpr int THREADS = 256;                 // mark / write: 4 waves, one workspace slot per workgroup
-constexpr int WAVES = THREADS / TN_WAVE;
+constexpr int THREADS = tn::COMPACT_THREADS; // mark / write: 4 waves, one workspace slot per workgroup
 constexpr int SCAN_THREADS = 1024;           // scan: workgroup counts per trip of its loop
 
 struct PointsArgs {
@@ -50,64 +49,25 @@ __device__ __forceinline__ bool keeps(const PointsArgs &a, int64_t r)
 
 __global__ __launch_bounds__(THREADS) void points_mark_kernel(PointsArgs a, uint64_t *__restrict__ ballots, int64_t *__restrict__ group)
 {
-    __shared__ int wave_kept[WAVES];
-    const int tid = (int)threadIdx.x, wave = tid / TN_WAVE;
-    const int64_t r = (int64_t)blockIdx.x * THREADS + tid;
-    const bool keep = r < a.n && keeps(a, r);                 // (lanes past n stay in the ballot with a 0 bit)
-    const uint64_t m = __ballot(keep);
-    if (tn::lane_id() == 0) {
-        if ((int64_t)blockIdx.x * THREADS + wave * TN_WAVE < a.n) ballots[(int64_t)blockIdx.x * WAVES + wave] = m;
-        wave_kept[wave] = __popcll(m);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int s = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) s += wave_kept[w];
-        group[blockIdx.x] = s;
-    }
+    const int64_t r = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+    const bool keep[1] = {r < a.n && keeps(a, r)};               // (lanes past n stay in the ballot with a 0 bit)
+    tn::compact_mark<1, 1>(keep, ballots, group, gridDim.x);
 }
 
 // group[0..n_groups): counts in, exclusive offsets out (a total stays below 2^31: n does)
 __global__ __launch_bounds__(SCAN_THREADS) void points_scan_kernel(int64_t *__restrict__ group, int64_t n_groups, int64_t *__restrict__ count)
 {
-    constexpr int SW = SCAN_THREADS / TN_WAVE;
-    __shared__ int wave_total[SW];
-    const int tid = (int)threadIdx.x, lane = tn::lane_id(), wave = tid / TN_WAVE;
-    int64_t carry = 0;
-    for (int64_t base = 0; base < n_groups; base += SCAN_THREADS) {       // (trip count uniform over the workgroup)
-        const int64_t i = base + tid;
-        const int v = i < n_groups ? (int)group[i] : 0;
-        const int s = tn::wave_scan(v);
-        if (lane == TN_WAVE - 1) wave_total[wave] = s;
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < SW; ++w) {
-            const int t = wave_total[w];
-            before += w < wave ? t : 0;
-            total += t;
-        }
-        if (i < n_groups) group[i] = carry + before + (s - v);
-        carry += total;
-        __syncthreads();                                                 // wave_total is rewritten by the next trip
-    }
-    if (tid == 0) *count = carry;
+    tn::scan_group_counts<SCAN_THREADS>(group, n_groups, count);
 }
 
 __global__ __launch_bounds__(THREADS) void points_write_kernel(PointsArgs a, const uint64_t *__restrict__ ballots, const int64_t *__restrict__ group,
                                                                int64_t capacity, float *__restrict__ points, uint8_t *__restrict__ colors,
                                                                int32_t *__restrict__ src)
 {
-    const int tid = (int)threadIdx.x, wave = tid / TN_WAVE;
-    const int64_t r = (int64_t)blockIdx.x * THREADS + tid;
+    const int64_t r = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (r >= a.n) return;
-    const uint64_t *b = ballots + (int64_t)blockIdx.x * WAVES;          // (waves below a lane with r < n all start below n: their ballots exist)
-    const uint64_t m = b[wave];
-    if (!((m >> tn::lane_id()) & 1)) return;
-    int64_t rank = group[blockIdx.x] + tn::rank_below(m);
-    for (int w = 0; w < wave; ++w) rank += __popcll(b[w]);
-    if (rank >= capacity) return;
+    const int64_t rank = tn::compact_rank<1>(ballots, group, 0);
+    if (rank < 0 || rank >= capacity) return;
     const float op = a.opacity[r];
     float p[3];
     point_of(a, r, a.depth[r], p);
@@ -122,15 +82,13 @@ __global__ __launch_bounds__(THREADS) void points_write_kernel(PointsArgs a, con
     src[rank] = (int32_t)r;
 }
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 }  // namespace
 
 extern "C" int tn_points_workspace_bytes(int64_t n, int64_t *bytes)
 {
     TN_REQUIRE(bytes, TN_E_NULL, "tn_points_workspace_bytes: null pointer");
     TN_REQUIRE(n >= 0 && n < ((int64_t)1 << 31), TN_E_SIZE, "tn_points_workspace_bytes: n must be in [0, 2^31)");
-    *bytes = 8 * ceil_div(n, TN_WAVE) + 8 * ceil_div(n, THREADS);
+    *bytes = tn::compact_bytes<1, 1>(tn::ceil_div(n, THREADS));
     return TN_OK;
 }
 
@@ -144,20 +102,13 @@ extern "C" int tn_points_compact(const float *rays_o, const float *rays_d, const
     TN_REQUIRE(count, TN_E_NULL, "tn_points_compact: null pointer (count)");
     TN_REQUIRE(capacity == 0 || (points && colors && src), TN_E_NULL, "tn_points_compact: null output pointer with capacity > 0");
     hipStream_t s = (hipStream_t)stream;
-    if (n == 0) {
-        hipError_t e = hipMemsetAsync(count, 0, sizeof(int64_t), s);
-        if (e != hipSuccess) {
-            tn::set_error("tn_points_compact: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        return TN_OK;
-    }
+    if (n == 0) return tn::zero_bytes(count, sizeof(int64_t), s, "tn_points_compact");
     TN_REQUIRE(rays_o && rays_d && rgb && opacity && depth && workspace, TN_E_NULL, "tn_points_compact: null pointer");
     TN_REQUIRE(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)count & 7) == 0, TN_E_ALIGN, "tn_points_compact: workspace and count must be 8-byte aligned");
     const PointsArgs a = {rays_o, rays_d, rgb, opacity, depth, bg, box, min_opacity, n};
-    const int64_t n_groups = ceil_div(n, THREADS);
+    const int64_t n_groups = tn::ceil_div(n, THREADS);
     uint64_t *ballots = (uint64_t *)workspace;
-    int64_t *group = (int64_t *)workspace + ceil_div(n, TN_WAVE);
+    int64_t *group = tn::compact_group<1>(workspace, n_groups);
     points_mark_kernel<<<dim3((unsigned)n_groups), dim3(THREADS), 0, s>>>(a, ballots, group);
     int rc = tn::check_launch("points_mark_kernel");
     if (rc != TN_OK) return rc;

@@ -26,6 +26,18 @@ inline int check_launch(const char *kernel) {
     return TN_OK;
 }
 
+inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// zeroes `bytes` bytes at p on the stream; a failure is reported in the name of the entry point `who`
+inline int zero_bytes(void *p, size_t bytes, hipStream_t s, const char *who) {
+    hipError_t e = hipMemsetAsync(p, 0, bytes, s);
+    if (e != hipSuccess) {
+        set_error("%s: %s", who, hipGetErrorString(e));
+        return (int)e;
+    }
+    return TN_OK;
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }
 
 // number of set bits of `m` strictly below this lane

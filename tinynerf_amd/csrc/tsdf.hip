@@ -17,7 +17,7 @@
 // tn_tsdf_mask_faces -- two launches: per cell whose id in the extractor's map is >= 0, observed[id] = all 8 corner weights > 0;
 //   per face, (-1, -1, -1) when an index lies outside [0, V) or names a vertex that is not observed.
 #include <cmath>
-#include "tn_common.h"
+#include "grid_device.h"
 
 namespace {
 
@@ -42,10 +42,8 @@ __global__ __launch_bounds__(THREADS) void tsdf_integrate_kernel(tn_camera_table
 {
     const int64_t m = (int64_t)blockIdx.x * THREADS + threadIdx.x;
     if (m >= g.nodes) return;
-    const uint32_t row = (uint32_t)m / (uint32_t)g.sx, k = row / (uint32_t)g.sy;
-    const float x0 = fmaf((float)((uint32_t)m - row * (uint32_t)g.sx), g.h[0], g.lo[0]);
-    const float x1 = fmaf((float)(row - k * (uint32_t)g.sy), g.h[1], g.lo[1]);
-    const float x2 = fmaf((float)k, g.h[2], g.lo[2]);
+    float x[3];
+    tn::node_position<uint32_t>((uint32_t)m, (uint32_t)g.sx, (uint32_t)g.sy, g.lo, g.h, x);      // (32-bit divisions: nodes < 2^31)
     // (the table is read-only for the launch and `view` is the same in every lane: these become scalar loads)
     const float *__restrict__ c2w = cams.c2w;
     const float *__restrict__ lens = cams.lens;
@@ -55,7 +53,7 @@ __global__ __launch_bounds__(THREADS) void tsdf_integrate_kernel(tn_camera_table
     float s_sum = S[m], w_sum = W[m];
     for (int view = view_first; view < view_first + view_count; ++view) {
         const float *M = c2w + 12 * (int64_t)view;
-        const float p0 = x0 - M[3], p1 = x1 - M[7], p2 = x2 - M[11];
+        const float p0 = x[0] - M[3], p1 = x[1] - M[7], p2 = x[2] - M[11];
         const float z = -fmaf(M[2], p0, fmaf(M[6], p1, M[10] * p2));
         if (!(z > 0.0f)) continue;                                // behind the camera (or NaN)
         const float qx = fmaf(M[0], p0, fmaf(M[4], p1, M[8] * p2)), qy = fmaf(M[1], p0, fmaf(M[5], p1, M[9] * p2));
@@ -109,12 +107,11 @@ __global__ __launch_bounds__(THREADS) void tsdf_observed_kernel(const float *__r
     if (c >= g.cells) return;
     const int32_t id = cell_ids[c];
     if ((uint32_t)id >= (uint32_t)n_vertices) return;             // -1: no vertex; an id that is not the extractor's writes nothing
-    const uint32_t row = (uint32_t)c / (uint32_t)g.nx, k = row / (uint32_t)g.ny;
-    const int64_t sy = (int64_t)g.nx + 1, sz = sy * ((int64_t)g.ny + 1);
-    const int64_t node = ((uint32_t)c - row * (uint32_t)g.nx) + sy * (row - k * (uint32_t)g.ny) + sz * k;
+    int idx[3];
+    int64_t node;
+    tn::cell_of(g.nx, g.ny, (uint32_t)c, idx, node);
     bool all = true;
-#pragma unroll
-    for (int d = 0; d < 8; ++d) all = all && W[node + (d & 1) + ((d >> 1) & 1) * sy + (d >> 2) * sz] > 0.0f;
+    tn::for_corners(g.nx, g.ny, node, [&](int, int64_t n) { all = all && W[n] > 0.0f; });
     observed[id] = all ? 1 : 0;
 }
 
@@ -132,19 +129,6 @@ __global__ __launch_bounds__(THREADS) void tsdf_mask_kernel(const uint8_t *__res
     if (!keep) faces[3 * f] = -1, faces[3 * f + 1] = -1, faces[3 * f + 2] = -1;
 }
 
-int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-// the number of a grid's nodes (cells = false) or cells, 0 with an empty axis, -1 for a negative dim or 2^31 or more
-int64_t grid_count(const int32_t *dims, bool cells)
-{
-    const int64_t limit = (int64_t)1 << 31;
-    if (dims[0] < 0 || dims[1] < 0 || dims[2] < 0) return -1;
-    if (dims[0] == 0 || dims[1] == 0 || dims[2] == 0) return 0;
-    const int64_t e = cells ? 0 : 1, xy = (dims[0] + e) * (dims[1] + e);      // (< 2^62)
-    if (xy >= limit || xy * (dims[2] + e) >= limit) return -1;
-    return xy * (dims[2] + e);
-}
-
 }  // namespace
 
 extern "C" int tn_tsdf_integrate(const tn_camera_table *cams, const float *depth, const float *opacity, float min_opacity, const int32_t *dims,
@@ -152,7 +136,7 @@ extern "C" int tn_tsdf_integrate(const tn_camera_table *cams, const float *depth
                                  void *stream)
 {
     TN_REQUIRE(cams && dims && lo && h, TN_E_NULL, "tn_tsdf_integrate: null pointer (cams, dims, lo, h)");
-    const int64_t nodes = grid_count(dims, false);
+    const int64_t nodes = tn::grid_count(dims, true);
     TN_REQUIRE(nodes >= 0, TN_E_SIZE, "tn_tsdf_integrate: dims must be >= 0 with fewer than 2^31 nodes");
     TN_REQUIRE(view_first >= 0 && view_count >= 0 && cams->n_img >= 0 && view_count <= cams->n_img && view_first <= cams->n_img - view_count, TN_E_SIZE,
                "tn_tsdf_integrate: view_first .. view_first + view_count must lie inside the camera table");
@@ -168,7 +152,7 @@ extern "C" int tn_tsdf_integrate(const tn_camera_table *cams, const float *depth
     g.nodes = nodes;
     for (int a = 0; a < 3; ++a) g.lo[a] = lo[a], g.h[a] = h[a];
     g.trunc = trunc, g.min_opacity = min_opacity;
-    tsdf_integrate_kernel<<<dim3((unsigned)ceil_div(nodes, THREADS)), dim3(THREADS), 0, (hipStream_t)stream>>>(*cams, depth, opacity, g, view_first,
+    tsdf_integrate_kernel<<<dim3((unsigned)tn::ceil_div(nodes, THREADS)), dim3(THREADS), 0, (hipStream_t)stream>>>(*cams, depth, opacity, g, view_first,
                                                                                                            view_count, S, W);
     return tn::check_launch("tsdf_integrate_kernel");
 }
@@ -177,8 +161,8 @@ extern "C" int tn_tsdf_mask_faces(const float *W, const int32_t *dims, const int
                                   uint8_t *observed, void *stream)
 {
     TN_REQUIRE(dims, TN_E_NULL, "tn_tsdf_mask_faces: null pointer (dims)");
-    const int64_t cells = grid_count(dims, true), limit = (int64_t)1 << 31;
-    TN_REQUIRE(cells >= 0 && grid_count(dims, false) >= 0, TN_E_SIZE, "tn_tsdf_mask_faces: dims must be >= 0 with fewer than 2^31 nodes");
+    const int64_t cells = tn::grid_count(dims, false), limit = (int64_t)1 << 31;
+    TN_REQUIRE(cells >= 0 && tn::grid_count(dims, true) >= 0, TN_E_SIZE, "tn_tsdf_mask_faces: dims must be >= 0 with fewer than 2^31 nodes");
     TN_REQUIRE(n_vertices >= 0 && n_faces >= 0 && n_vertices < limit && n_faces < limit, TN_E_SIZE,
                "tn_tsdf_mask_faces: n_vertices and n_faces must be >= 0 and below 2^31 (vertex ids are int32)");
     if (n_faces == 0) return TN_OK;
@@ -189,20 +173,16 @@ extern "C" int tn_tsdf_mask_faces(const float *W, const int32_t *dims, const int
                "tn_tsdf_mask_faces: W, cell_ids and faces must be 4-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     if (n_vertices > 0) {
-        hipError_t e = hipMemsetAsync(observed, 0, (size_t)n_vertices, s);      // a vertex no cell names is not observed
-        if (e != hipSuccess) {
-            tn::set_error("tn_tsdf_mask_faces: %s", hipGetErrorString(e));
-            return (int)e;
-        }
+        if (int rc = tn::zero_bytes(observed, (size_t)n_vertices, s, "tn_tsdf_mask_faces")) return rc;      // a vertex no cell names is not observed
         if (cells > 0) {
             MaskGrid g;
             g.nx = dims[0], g.ny = dims[1];
             g.cells = cells;
-            tsdf_observed_kernel<<<dim3((unsigned)ceil_div(cells, THREADS)), dim3(THREADS), 0, s>>>(W, g, cell_ids, (int32_t)n_vertices, observed);
+            tsdf_observed_kernel<<<dim3((unsigned)tn::ceil_div(cells, THREADS)), dim3(THREADS), 0, s>>>(W, g, cell_ids, (int32_t)n_vertices, observed);
             const int rc = tn::check_launch("tsdf_observed_kernel");
             if (rc != TN_OK) return rc;
         }
     }
-    tsdf_mask_kernel<<<dim3((unsigned)ceil_div(n_faces, THREADS)), dim3(THREADS), 0, s>>>(observed, (int32_t)n_vertices, n_faces, faces);
+    tsdf_mask_kernel<<<dim3((unsigned)tn::ceil_div(n_faces, THREADS)), dim3(THREADS), 0, s>>>(observed, (int32_t)n_vertices, n_faces, faces);
     return tn::check_launch("tsdf_mask_kernel");
 }

@@ -108,16 +108,30 @@ def _extract(values, lo, h, level, normals, capacity, return_cells):
     return out + (cells(vcap > 0 or fcap > 0),) if return_cells else out
 
 
+def cut_box(box, dims: Sequence[int], who: Optional[str] = None):
+    """``(lo, h, dims)``: ``box`` (lo xyz, hi xyz) cut into ``dims = (nx, ny, nz)`` cells -- ``lo`` and ``h = extent / dims`` rounded to
+    float32, as the kernels use them.  With ``who``, box and dims are checked first (``ValueError`` in that name) and an axis of 0
+    cells keeps its whole extent as ``h``."""
+    box = np.asarray(box, np.float64).reshape(6)
+    dims = tuple(int(d) for d in dims)
+    cells = np.float64(dims)
+    if who is not None:
+        if len(dims) != 3 or min(dims) < 0:
+            raise ValueError(f"{who}: dims must be three cell counts >= 0")
+        if not np.isfinite(box).all() or not (box[3:] > box[:3]).all():
+            raise ValueError(f"{who}: the box must be finite with a positive extent on every axis")
+        cells = np.maximum(cells, 1.0)
+    return box[:3].astype(np.float32), ((box[3:] - box[:3]) / cells).astype(np.float32), dims
+
+
 def grid_dims(box, resolution: int):
     """``(lo, h, dims)``: ``resolution`` cells on the longest axis of ``box`` (lo xyz, hi xyz), ``ceil(resolution extent / longest)``
-    on the others -- near-cubic cells; ``lo`` and ``h = extent / cells`` rounded to float32, as the kernels use them"""
+    on the others -- near-cubic cells; ``lo`` and ``h`` from ``cut_box``"""
     box = np.asarray(box, np.float64).reshape(6)
     extent = box[3:] - box[:3]
     if int(resolution) < 1 or not (extent > 0).all() or not np.isfinite(box).all():
         raise ValueError("mesh: resolution must be >= 1 and the box finite with a positive extent on every axis")
-    dims = [max(1, int(math.ceil(int(resolution) * e / extent.max() - 1e-9))) for e in extent]
-    lo = box[:3].astype(np.float32)
-    return lo, (extent / np.float64(dims)).astype(np.float32), tuple(dims)
+    return cut_box(box, [max(1, int(math.ceil(int(resolution) * e / extent.max() - 1e-9))) for e in extent])
 
 
 @torch.no_grad()
@@ -139,9 +153,7 @@ def density_grid(trainer, box, dims: Sequence[int], chunk: int = 1 << 21):
     """``(values [nz+1, ny+1, nx+1], lo, h)``: ``log(max(sigma, 1e-30))`` of the trainer's density at the nodes of ``box`` (lo xyz, hi xyz)
     cut into ``dims = (nx, ny, nz)`` cells -- the nodes from ``tn_grid_nodes``, contracted with the trainer's contraction,
     ``trainer.sigma_fn`` under ``no_grad``, ``chunk`` nodes per call"""
-    box = np.asarray(box, np.float64).reshape(6)
-    dims = tuple(int(d) for d in dims)
-    lo, h = box[:3].astype(np.float32), ((box[3:] - box[:3]) / np.float64(dims)).astype(np.float32)
+    lo, h, dims = cut_box(box, dims)
     trainer.renderer.eval()
     return _log_density(trainer.sigma_fn, trainer.ray_provider.contraction, lo, h, dims, trainer.device, chunk), lo, h
 
@@ -188,26 +200,48 @@ def vertex_colors(trainer, vertices: torch.Tensor, normals: torch.Tensor, chunk:
     return out
 
 
+def _one_rank(who, trainer):
+    if getattr(trainer, "world", 1) > 1:
+        raise ValueError(f"{who} runs on one rank: world_size > 1 is not supported")
+
+
+def _export_grid(who, trainer, crop, resolution, level, default, what):
+    """``(box, lo, h, dims, level)`` of an export: the grid ``grid_dims(crop, resolution)`` (``crop`` ``None``:
+    ``points.default_crop``) and ``level`` (``None``: ``default(h)``), which must be finite and > 0 -- ``what`` says of what"""
+    from .points import default_crop
+    box = default_crop(trainer.cfg) if crop is None else crop
+    lo, h, dims = grid_dims(box, resolution)
+    level = default(h) if level is None else float(level)
+    if not (math.isfinite(level) and level > 0.0):
+        raise ValueError(f"{who}: {what} must be finite and > 0")
+    return box, lo, h, dims, level
+
+
+def _density_surface(trainer, lo, h, dims, sigma):
+    trainer.renderer.eval()
+    values = _log_density(trainer.sigma_fn, trainer.ray_provider.contraction, lo, h, dims, trainer.device, 1 << 21)
+    return extract(values, lo, h, math.log(sigma))
+
+
+def _finish_export(trainer, path, vertices, normals, faces, colors):
+    """the end of every mesh export: colours from ``vertex_colors`` (zeros when switched off or without vertices), ``path`` written
+    (``write_mesh_ply``) when one is given -> ``(vertices, normals, colors, faces)``"""
+    rgb = vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=vertices.device)
+    if path is not None:
+        write_mesh_ply(path, vertices, normals, rgb, faces)
+    return vertices, normals, rgb, faces
+
+
 @torch.no_grad()
 def export_mesh(trainer, path=None, resolution: int = 256, level: Optional[float] = None, crop=None, colors: bool = True):
     """The mesh of the trainer's density inside ``crop`` (6 values, lo xyz then hi xyz; ``None``: ``points.default_crop`` of its
     configuration) on ``grid_dims(crop, resolution)``, at the density ``level`` (default ``default_level``).  Returns ``(vertices [V,3]
     float32, normals [V,3] float32, colors [V,3] uint8, faces [F,3] int32)`` on the device -- ``colors`` (``vertex_colors``) zeros
     when switched off -- and writes ``path`` (``write_mesh_ply``) when one is given."""
-    if getattr(trainer, "world", 1) > 1:
-        raise ValueError("export_mesh runs on one rank: world_size > 1 is not supported")
-    from .points import default_crop
-    lo, h, dims = grid_dims(default_crop(trainer.cfg) if crop is None else crop, resolution)
-    sigma = default_level(h) if level is None else float(level)
-    if not sigma > 0.0 or not math.isfinite(sigma):
-        raise ValueError("export_mesh: level is a density: it must be finite and > 0")
-    trainer.renderer.eval()
-    values = _log_density(trainer.sigma_fn, trainer.ray_provider.contraction, lo, h, dims, trainer.device, 1 << 21)
-    vertices, normals, faces = extract(values, lo, h, math.log(sigma))
-    rgb = vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=vertices.device)
-    if path is not None:
-        write_mesh_ply(path, vertices, normals, rgb, faces)
-    return vertices, normals, rgb, faces
+    _one_rank("export_mesh", trainer)
+    _, lo, h, dims, sigma = _export_grid("export_mesh", trainer, crop, resolution, level, default_level, "level is a density: it")
+    vertices, normals, faces = _density_surface(trainer, lo, h, dims, sigma)
+    return _finish_export(trainer, path, vertices, normals, faces, colors)
 
 
 def components(faces: torch.Tensor, n_vertices: int):
@@ -289,24 +323,14 @@ def export_clean_mesh(trainer, path=None, resolution: int = 256, level: Optional
     """``export_mesh`` with ``filter_components(min_faces, keep_fraction)`` between the extraction and the colours: floaters and
     fragments below the threshold leave the mesh, and the colour decoder is only asked about vertices that stay.  With both options
     at 0 it returns and writes exactly what ``export_mesh`` does."""
-    if getattr(trainer, "world", 1) > 1:
-        raise ValueError("export_clean_mesh runs on one rank: world_size > 1 is not supported")
+    _one_rank("export_clean_mesh", trainer)
     component_threshold(min_faces, keep_fraction, 0)
     if not min_faces and not keep_fraction:
         return export_mesh(trainer, path, resolution=resolution, level=level, crop=crop, colors=colors)
-    from .points import default_crop
-    lo, h, dims = grid_dims(default_crop(trainer.cfg) if crop is None else crop, resolution)
-    sigma = default_level(h) if level is None else float(level)
-    if not sigma > 0.0 or not math.isfinite(sigma):
-        raise ValueError("export_clean_mesh: level is a density: it must be finite and > 0")
-    trainer.renderer.eval()
-    values = _log_density(trainer.sigma_fn, trainer.ray_provider.contraction, lo, h, dims, trainer.device, 1 << 21)
-    vertices, normals, faces = extract(values, lo, h, math.log(sigma))
+    _, lo, h, dims, sigma = _export_grid("export_clean_mesh", trainer, crop, resolution, level, default_level, "level is a density: it")
+    vertices, normals, faces = _density_surface(trainer, lo, h, dims, sigma)
     vertices, normals, _, faces = filter_components(vertices, normals, None, faces, min_faces=min_faces, keep_fraction=keep_fraction)
-    rgb = vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=vertices.device)
-    if path is not None:
-        write_mesh_ply(path, vertices, normals, rgb, faces)
-    return vertices, normals, rgb, faces
+    return _finish_export(trainer, path, vertices, normals, faces, colors)
 
 
 def _host(x, dtype) -> np.ndarray:

@@ -21,24 +21,13 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .mesh import _grid
+from .mesh import _grid, cut_box
 from .rays import CameraRays
 
 # Views per launch.  Every split gives the same bytes (the definition), so this is a matter of time alone: all views in one launch make
 # every workgroup sweep every map, chunks cost 8 B of read-modify-write per node and launch.  Measured (scripts/tsdf_time.py):
 # 100 views of 200 x 200 into 257^3 nodes take 6.3 ms in one launch, 3.3 ms at 16 views per launch, 6.4 ms at one view per launch.
 VIEWS_PER_LAUNCH = 16
-
-
-def _box_grid(box, dims):
-    """``(lo, h)`` as float32, the way ``mesh.density_grid`` cuts a box into ``dims`` cells"""
-    box = np.asarray(box, np.float64).reshape(6)
-    dims = tuple(int(d) for d in dims)
-    if len(dims) != 3 or min(dims) < 0:
-        raise ValueError("tsdf: dims must be three cell counts >= 0")
-    if not np.isfinite(box).all() or not (box[3:] > box[:3]).all():
-        raise ValueError("tsdf: the box must be finite with a positive extent on every axis")
-    return box[:3].astype(np.float32), ((box[3:] - box[:3]) / np.maximum(np.float64(dims), 1.0)).astype(np.float32), dims
 
 
 def integrate(cams: CameraRays, depth: torch.Tensor, opacity: Optional[torch.Tensor], box, dims: Sequence[int], trunc: float,
@@ -49,7 +38,7 @@ def integrate(cams: CameraRays, depth: torch.Tensor, opacity: Optional[torch.Ten
     holds one distance along the unit ray per pixel of the table, in its flat pixel order; ``opacity`` likewise, or ``None`` (then
     ``min_opacity`` is not used).  ``state``: the ``(S, W)`` of an earlier call, added to IN PLACE (``None``: zeros).  ``views``:
     ``(first, count)`` (``None``: all).  The views go to the kernel ``VIEWS_PER_LAUNCH`` at a time; every split gives the same bytes."""
-    lo, h, dims = _box_grid(box, dims)
+    lo, h, dims = cut_box(box, dims, "tsdf")
     if not (math.isfinite(float(trunc)) and float(trunc) > 0.0):
         raise ValueError("tsdf.integrate: trunc must be finite and > 0")
     first, count = (0, cams.n_img) if views is None else (int(views[0]), int(views[1]))
@@ -129,18 +118,13 @@ def export_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: 
     and ``mesh.filter_components(max(1, min_faces), keep_fraction)`` -- which drops the masked faces and orphaned vertices, and the
     pieces below the threshold.  Returns ``(vertices, normals, colors, faces)`` on the device as ``mesh.export_mesh`` does -- colours
     from ``mesh.vertex_colors``, zeros when switched off -- and writes ``path`` (``mesh.write_mesh_ply``) when one is given."""
-    if getattr(trainer, "world", 1) > 1:
-        raise ValueError("export_tsdf_mesh runs on one rank: world_size > 1 is not supported")
     from . import mesh as M
-    from .points import DEPTH_KEYS, default_crop
+    from .points import DEPTH_KEYS
+    M._one_rank("export_tsdf_mesh", trainer)
     M.component_threshold(min_faces, keep_fraction, 0)             # the arguments, before any device work
     if depth not in DEPTH_KEYS:
         raise ValueError(f"export_tsdf_mesh: depth must be one of {sorted(DEPTH_KEYS)}, not {depth!r}")
-    box = default_crop(trainer.cfg) if crop is None else crop
-    lo, h, dims = M.grid_dims(box, resolution)
-    trunc = 4.0 * float(np.max(h)) if trunc is None else float(trunc)
-    if not (math.isfinite(trunc) and trunc > 0.0):
-        raise ValueError("export_tsdf_mesh: trunc must be finite and > 0")
+    box, lo, h, dims, trunc = M._export_grid("export_tsdf_mesh", trainer, crop, resolution, trunc, lambda h: 4.0 * float(np.max(h)), "trunc")
     idx = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
     dev = trainer.device
     S = torch.zeros((dims[2] + 1, dims[1] + 1, dims[0] + 1), dtype=torch.float32, device=dev)
@@ -157,11 +141,8 @@ def export_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: 
             maps = trainer.render_rays(o, d, maps=True)
             dist[cams.offsets[k]:cams.offsets[k + 1]] = maps[DEPTH_KEYS[depth]].reshape(-1)
             opacity[cams.offsets[k]:cams.offsets[k + 1]] = maps["opacity"].reshape(-1)
-        integrate(cams, dist, opacity, box, dims, trunc, state=(S, W))          # (the same box and dims: grid_dims' lo and h, bit for bit)
+        integrate(cams, dist, opacity, box, dims, trunc, state=(S, W))          # (box and dims give lo and h again: cut_box both times)
     vertices, normals, faces, cells = M.extract_with_cells(field(S, W), lo, h, 0.0)
     faces = mask_faces(W, dims, cells, vertices.size(0), faces)
     vertices, normals, _, faces = M.filter_components(vertices, normals, None, faces, min_faces=max(1, int(min_faces)), keep_fraction=keep_fraction)
-    rgb = M.vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=dev)
-    if path is not None:
-        M.write_mesh_ply(path, vertices, normals, rgb, faces)
-    return vertices, normals, rgb, faces
+    return M._finish_export(trainer, path, vertices, normals, faces, colors)
