@@ -588,7 +588,8 @@ int tn_kplanes_mlp_bwd_pair(const tn_kplanes_desc *kdesc, const float *coords, i
  *   out[n,k] = act(sum_c f[n,c] * basis[n,k,c]),   f [n,C], basis [n,K,C] row-major, 1 <= K <= 4.
  * Opacity decoder: basis = Linear(f) (K = 1), act = TN_ACT_EXP_M1 (exp(v - 1) with the truncated exponential's backward clamp,
  * models.py:42-55); colour decoder: basis = MLP([PE(d), d, f]).view(n, 3, C), act = TN_ACT_SIGMOID.
- * Backward: grad_basis [n,K,C] (may be NULL) is written, grad_f [n,C] is written or (accumulate_f) added to. */
+ * Backward: grad_basis [n,K,C] (may be NULL) is written, grad_f [n,C] is written or (accumulate_f) added to: the sum over k is
+ * finished first and added to what grad_f held in one addition. */
 int tn_basis_dot_fwd(const float *f, const float *basis, int64_t n, int32_t channels, int32_t n_out, int32_t activation,
                      float *out, void *stream);
 int tn_basis_dot_bwd(const float *f, const float *basis, const float *grad_out, int64_t n, int32_t channels, int32_t n_out,

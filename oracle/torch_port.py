@@ -225,20 +225,27 @@ def features(sd: Dict[str, torch.Tensor], x: torch.Tensor, vanilla_freqs: int = 
 
 
 def render(sd: Dict[str, torch.Tensor], packed: torch.Tensor, info: torch.Tensor, bg: Optional[torch.Tensor],
-           thr: float = 1e-4, vanilla_freqs: int = 0, cobafa_freqs=None, hashgrid=None) -> torch.Tensor:
+           thr: float = 1e-4, vanilla_freqs: int = 0, cobafa_freqs=None, hashgrid=None, explicit: bool = False) -> torch.Tensor:
     """core.py:225-267 for a K-Planes (or Vanilla: vanilla_freqs > 0, or Cobafa: cobafa_freqs, or hash grid: hashgrid = its level
-    plan) field with the Vanilla decoders."""
+    plan) field with the Vanilla decoders, or (``explicit``) with the explicit K-Planes decoders of models.py:183-205."""
     n, R = packed.size(0), info.size(0)
     x = packed[:, :3]
     feat = features(sd, x, vanilla_freqs, cobafa_freqs, hashgrid)
-    sig = _TruncExp.apply(mlp(sd, "sigma_decoder.net.net.", feat) - 1.).ravel()
+    if explicit:
+        sig = explicit_sigma(sd, feat, "sigma_decoder.").ravel()
+    else:
+        sig = _TruncExp.apply(mlp(sd, "sigma_decoder.net.net.", feat) - 1.).ravel()
     w = _Weights.apply(sig, packed[:, 6].contiguous(), info, thr)
     mask = w > 0
     rgbs = torch.zeros((n, 3), dtype=feat.dtype)          # (fp32 as the reference runs; a float64 state dict and batch render in float64)
     if mask.any():
         d = packed[:, 3:6][mask]
-        inp = torch.cat([posenc(d, sd["rgb_decoder.pe.freqs"]), d, feat[mask]], -1)
-        rgbs = rgbs.index_put((torch.nonzero(mask).squeeze(1),), torch.sigmoid(mlp(sd, "rgb_decoder.net.net.", inp)))
+        if explicit:
+            rgb = explicit_rgb(sd, feat[mask], d, "rgb_decoder.")
+        else:
+            inp = torch.cat([posenc(d, sd["rgb_decoder.pe.freqs"]), d, feat[mask]], -1)
+            rgb = torch.sigmoid(mlp(sd, "rgb_decoder.net.net.", inp))
+        rgbs = rgbs.index_put((torch.nonzero(mask).squeeze(1),), rgb)
         rgbs = rgbs * w[:, None]
     else:                                      # core.py:251-254 "Empty iteration": fresh leaves, no parameter is reached
         rgbs = torch.zeros((n, 3), requires_grad=True)

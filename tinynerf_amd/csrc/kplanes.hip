@@ -155,12 +155,13 @@ __global__ __launch_bounds__(256) void basis_dot_bwd_kernel(const float *__restr
         }
         for (int c = lane; c < C; c += 64) {
             const float fc = fi[c];
-            float a = accumulate_f ? g_f[i * C + c] : 0.0f;
+            float a = 0.0f;
             for (int k = 0; k < K; ++k) {
                 a += gv[k] * bi[k * C + c];
                 if (g_basis) g_basis[(i * K + k) * C + c] = gv[k] * fc;
             }
-            g_f[i * C + c] = a;
+            // accumulate_f: the finished sum is added ONCE to what was there (a running sum that starts from it rounds it K times)
+            g_f[i * C + c] = accumulate_f ? g_f[i * C + c] + a : a;
         }
     }
 }
