@@ -886,6 +886,57 @@ int tn_tsdf_mask_faces(const float *W,                                          
                        int64_t n_faces,
                        uint8_t *observed,                                       /* [n_vertices] scratch */
                        void *stream);
+/* The colour half of the TSDF: the rendered images fused into a colour volume on the same grid, and the volume sampled at mesh
+ * vertices.  fp32 throughout, every fused multiply-add an explicit fmaf, the divisions and roots correctly rounded.
+ * State.  Four floats per node, in tn_tsdf_integrate's node order: C[node] = (sum w r, sum w g, sum w b, sum w).  The caller zeroes C
+ *   before the first call; every call adds to it.
+ * Inputs.  tn_tsdf_integrate's (table, depth, opacity or NULL with min_opacity, trunc, a range of views) and rgb [n_pixels][3], the
+ *   composited colour of every pixel in the table's flat pixel order, with bg [3] on the device, the colour it was composited over
+ *   (NULL: (0, 0, 0)).
+ * Update of node x, for the views of the range in ASCENDING order.  Steps 1-5 are exactly tn_tsdf_integrate's (camera frame, lens,
+ *   monotonicity guard, pixel g, depth gate and opacity gate).  Then sdf = D - |p| as in step 6, and the view contributes when
+ *   -trunc <= sdf <= trunc, with the weight w = 1 - |sdf| / trunc (a correctly rounded division): triangular, zero at both edges of
+ *   the band, so nothing jumps there; free space in front of the band votes on geometry and says nothing about colour.  The colour
+ *   is the expected colour given a hit, the background taken out again, exactly tn_points_compact's:
+ *     u_c = fmaf(-(1 - opacity[g]), bg_c, rgb[g][c]) / opacity[g], clamped to [0, 1] with NaN -> 0
+ *   (opacity == NULL: the opacity is 1, u_c = rgb[g][c] clamped).  C[node][c] = fmaf(w, u_c, C[node][c]), C[node][3] += w.
+ *   No atomics, one lane owns a node: a range of views in one call and the same range split over calls in order give the same bytes.
+ * tn_tsdf_integrate_color: one launch on `stream`, one lane per node, 256 per workgroup, i fastest, the loop over the views inside
+ *   the kernel; a view's table row is read with wave-uniform (scalar) loads, the node's four accumulators with one 16-byte load
+ *   before the loop and one 16-byte store after it.  Checked before the launch: TN_E_NULL for null cams / dims / lo / h, then
+ *   TN_E_SIZE for a negative dim or count, a view range outside the table or 2^31 nodes or more; TN_E_CONFIG for a trunc that is not
+ *   finite or <= 0 and -- with an opacity map -- unless min_opacity > 0 (NaN included: the division must stay defined); TN_E_NULL for
+ *   a null table pointer (cams->rgb is not read) or null depth / rgb / C (opacity and bg are optional); TN_E_ALIGN: 4 bytes for the
+ *   maps and bg, 16 for C.  view_count == 0 or a dim of 0: TN_OK without a launch, C untouched.
+ * Sampling.  Per point p and axis c: g_c = (p_c - lo_c) / h_c (a subtraction, then a correctly rounded division), i_c =
+ *   min(max((int)floor(g_c), 0), n_c - 1), u_c = min(max(g_c - (float)i_c, 0), 1): a point outside the grid is clamped onto it (i_c is clamped as an integer, so it
+ *   stays inside the grid on an axis of more than 2^24 cells too, where (float)(n_c - 1) is no longer exact).  The
+ *   8 corners k = dx + 2 dy + 4 dz of cell (i_0, i_1, i_2), in that order, have the trilinear weights t_k = (a_0 a_1) a_2 with a_c =
+ *   u_c where the corner's d_c = 1 and 1 - u_c where it is 0.  num_c = sum_k t_k C[k][c] and den = sum_k t_k C[k][3], each a chain
+ *   fmaf(t_k, C[k][.], sum) in corner order starting from 0.  out = (num_0 / den, num_1 / den, num_2 / den, den) when den > 0, and
+ *   (0, 0, 0, 0) when den is not > 0 or a coordinate of p is not finite.  Corners without colour carry the weight 0: they drop out of
+ *   the average instead of darkening it.  The interpolant is continuous across cell faces.  The output is float; bytes are the
+ *   caller's business (tn_points_compact's rule: (uint8) fmaf(c, 255, 0.5)).
+ * tn_tsdf_sample_colors: one launch, one lane per point.  Checked before the launch: TN_E_NULL for null dims / lo / h; TN_E_SIZE for
+ *   a negative dim, 2^31 nodes or more, n < 0 or n >= 2^31; TN_E_NULL for null C / points / out; TN_E_ALIGN: 4 bytes for points, 16
+ *   for C and out.  n == 0 or a dim of 0: TN_OK without a launch.
+ * No reference call site: the reference renders images and exports no geometry. */
+int tn_tsdf_integrate_color(const tn_camera_table *cams,
+                            const float *depth,                                 /* [n_pixels] device */
+                            const float *opacity,                               /* [n_pixels] or NULL */
+                            float min_opacity,
+                            const float *rgb,                                   /* [n_pixels][3], the composited colour */
+                            const float *bg,                                    /* [3] device, or NULL = (0,0,0) */
+                            const int32_t *dims, const float *lo, const float *h,   /* host arrays of 3 */
+                            float trunc, int32_t view_first, int32_t view_count,
+                            float *C,                                           /* [(nx+1)(ny+1)(nz+1)][4] */
+                            void *stream);
+int tn_tsdf_sample_colors(const float *C,                                       /* [(nx+1)(ny+1)(nz+1)][4] */
+                          const int32_t *dims, const float *lo, const float *h, /* host arrays of 3 */
+                          const float *points,                                  /* [n,3] */
+                          int64_t n,
+                          float *out,                                           /* [n][4]: r, g, b, den */
+                          void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * optimizer step of the harness                      (reference run.py:186,258-260: torch.optim.Adam)

@@ -938,7 +938,7 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
           eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
           render_maps: bool = False, ssim: bool = False, pointcloud: int = 0, pointcloud_crop=None,
           mesh: int = 0, mesh_level: Optional[float] = None, mesh_crop=None, mesh_min_faces: int = 0, mesh_keep_fraction: float = 0.0,
-          tsdf_mesh: int = 0, tsdf_trunc: Optional[float] = None, normals: bool = False):
+          tsdf_mesh: int = 0, tsdf_trunc: Optional[float] = None, tsdf_colors: str = "decoder", normals: bool = False):
     """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device, or a data.CameraRaysDataset (a
     photographed scene: the trainer makes its rays from the camera table, ``Trainer(ray_source=...)``).  ``render_maps``: the final
     test render also writes the depth / opacity maps of every image (``infer(maps=True)``).  ``ssim``: the periodic evaluation and
@@ -956,8 +956,12 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
     ``tsdf_mesh`` > 0 (with `test_set` and `output`): after the final test render the test views' depth maps are fused into a TSDF and
     its zero level goes to ``tsdf_mesh.ply``, ``tsdf_mesh`` cells on the longest axis of the box (``tsdf.export_tsdf_mesh``, DESIGN 6j;
     ``tsdf_trunc``: its ``trunc``; ``mesh_crop``, ``mesh_min_faces`` and ``mesh_keep_fraction`` apply to it as well).  At 0 nothing of
-    it is imported, allocated or launched."""
+    it is imported, allocated or launched.  ``tsdf_colors``: ``"decoder"`` -- the colour decoder asked at every vertex, the file what
+    it always was -- or ``"fused"`` -- the test views' rendered colours fused into a colour volume beside the TSDF and sampled at the
+    vertices; ``ValueError`` for anything else, before the first step."""
     import json
+    if tsdf_colors not in ("decoder", "fused"):
+        raise ValueError(f"train(tsdf_colors=...): 'decoder' or 'fused', not {tsdf_colors!r}")
     if normals and cfg.method not in ("kplanes", "hashgrid"):
         raise ValueError(f"train(normals=True): method {cfg.method!r} has no analytic density gradient (kplanes and hashgrid only)")
     render_maps = render_maps or normals
@@ -1007,7 +1011,7 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
         if tsdf_mesh > 0 and output is not None:
             from .tsdf import export_tsdf_mesh
             export_tsdf_mesh(tr, test_set, output / "tsdf_mesh.ply", resolution=tsdf_mesh, trunc=tsdf_trunc, crop=mesh_crop,
-                             min_faces=mesh_min_faces, keep_fraction=mesh_keep_fraction)
+                             min_faces=mesh_min_faces, keep_fraction=mesh_keep_fraction, colors="fused" if tsdf_colors == "fused" else True)
         if render_maps:
             rendered = [r["rgb"] for r in rendered]
         if test_set.rgbs:

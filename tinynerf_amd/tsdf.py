@@ -4,10 +4,12 @@ level set of the raw density (``mesh.export_mesh``) the level is 0 whatever the 
 over the whole ray, so fog averages out, and views that disagree vote.
 
 * ``integrate`` -- ``tn_tsdf_integrate``: the views of a camera table and their depth maps added into ``(S, W)``;
+* ``integrate_color`` -- ``tn_tsdf_integrate_color``: the same views' rendered colours added into the colour volume ``C`` (DESIGN 6k);
+* ``sample_colors`` -- ``tn_tsdf_sample_colors``: the colour volume at points, e.g. the mesh's vertices;
 * ``field`` -- the mesh field ``-S / W`` (``-1`` where ``W == 0``), level 0, inside ``>= 0``;
 * ``mask_faces`` -- ``tn_tsdf_mask_faces``: faces of cells with an unobserved corner become ``(-1, -1, -1)``;
 * ``camera_table`` -- the pose-only ``rays.CameraRays`` of a ``PoseDataset`` / ``CameraPoseDataset``;
-* ``export_tsdf_mesh`` -- render, integrate, extract, mask, filter, colour, write.
+* ``export_tsdf_mesh`` -- render, integrate, extract, mask, filter, colour (the decoder's, or ``"fused"`` from the renders), write.
 
 torch is plumbing only; there is no CPU path.  No reference counterpart: the reference renders images and exports no geometry.
 """
@@ -27,6 +29,7 @@ from .rays import CameraRays
 # Views per launch.  Every split gives the same bytes (the definition), so this is a matter of time alone: all views in one launch make
 # every workgroup sweep every map, chunks cost 8 B of read-modify-write per node and launch.  Measured (scripts/tsdf_time.py):
 # 100 views of 200 x 200 into 257^3 nodes take 6.3 ms in one launch, 3.3 ms at 16 views per launch, 6.4 ms at one view per launch.
+# The colour pass (16 B per node and launch) has the same optimum: 6.6 ms, 3.5 ms and 10.1 ms.
 VIEWS_PER_LAUNCH = 16
 
 
@@ -62,6 +65,65 @@ def integrate(cams: CameraRays, depth: torch.Tensor, opacity: Optional[torch.Ten
         L.call("tn_tsdf_integrate", dev, C.byref(cams.table), L.ptr(depth), L.ptr(opacity), C.c_float(min_opacity), dims_c, lo_c, h_c,
                C.c_float(trunc), C.c_int32(v), C.c_int32(min(VIEWS_PER_LAUNCH, first + count - v)), L.ptr(S), L.ptr(W))
     return S, W
+
+
+def integrate_color(cams: CameraRays, depth: torch.Tensor, opacity: Optional[torch.Tensor], rgb: torch.Tensor, bg: Optional[torch.Tensor], box,
+                    dims: Sequence[int], trunc: float, min_opacity: float = 0.5, state: Optional[torch.Tensor] = None,
+                    views: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+    """``C``, float32 ``[nz+1, ny+1, nx+1, 4]`` on the device: ``(sum w r, sum w g, sum w b, sum w)`` per node of ``integrate``'s grid
+    -- the views' rendered colours ``rgb [n_pixels, 3]`` (composited over ``bg [3]``; ``None``: black), the background taken out
+    again, added at the weight ``w = 1 - |sdf| / trunc`` wherever a view puts the node within ``trunc`` of its surface
+    (include/tinynerf_hip.h has the definition).  ``depth``, ``opacity`` (with one, ``min_opacity`` must be ``> 0``), ``box``,
+    ``dims``, ``trunc`` and ``views`` are ``integrate``'s; ``state``: the ``C`` of an earlier call, added to IN PLACE (``None``:
+    zeros).  The views go to the kernel ``VIEWS_PER_LAUNCH`` at a time; every split gives the same bytes."""
+    lo, h, dims = cut_box(box, dims, "tsdf")
+    if not (math.isfinite(float(trunc)) and float(trunc) > 0.0):
+        raise ValueError("tsdf.integrate_color: trunc must be finite and > 0")
+    if opacity is not None and not float(min_opacity) > 0.0:
+        raise ValueError("tsdf.integrate_color: with an opacity map min_opacity must be > 0 (the colour is divided by the opacity)")
+    first, count = (0, cams.n_img) if views is None else (int(views[0]), int(views[1]))
+    if first < 0 or count < 0 or first + count > cams.n_img:
+        raise ValueError("tsdf.integrate_color: views must lie inside the camera table")
+    if depth.numel() != cams.n_rays or (opacity is not None and opacity.numel() != cams.n_rays) or rgb.numel() != 3 * cams.n_rays:
+        raise ValueError("tsdf.integrate_color: depth and opacity must hold one entry per pixel of the camera table, rgb three")
+    if depth.dtype != torch.float32 or (opacity is not None and opacity.dtype != torch.float32) or rgb.dtype != torch.float32:
+        raise ValueError("tsdf.integrate_color: depth, opacity and rgb must be float32")
+    if bg is not None and (bg.numel() != 3 or bg.dtype != torch.float32):
+        raise ValueError("tsdf.integrate_color: bg must be three float32 values")
+    shape = (dims[2] + 1, dims[1] + 1, dims[0] + 1, 4)
+    dev = L.require_cuda(cams.c2w, depth, opacity, rgb, bg)
+    if state is None:
+        vol = torch.zeros(shape, dtype=torch.float32, device=dev)
+    else:
+        vol = state
+        if tuple(vol.shape) != shape or vol.dtype != torch.float32:
+            raise ValueError("tsdf.integrate_color: state must be a float32 tensor [nz+1, ny+1, nx+1, 4]")
+        L.require_cuda(vol, depth)
+    lo_c, h_c, dims_c = _grid(lo, h, dims)
+    for v in range(first, first + count, VIEWS_PER_LAUNCH):
+        L.call("tn_tsdf_integrate_color", dev, C.byref(cams.table), L.ptr(depth), L.ptr(opacity), C.c_float(min_opacity), L.ptr(rgb), L.ptr(bg),
+               dims_c, lo_c, h_c, C.c_float(trunc), C.c_int32(v), C.c_int32(min(VIEWS_PER_LAUNCH, first + count - v)), L.ptr(vol))
+    return vol
+
+
+def sample_colors(C: torch.Tensor, box, dims: Sequence[int], points: torch.Tensor):
+    """``(rgb [n,3] float32, den [n] float32)``: the colour volume ``C`` of ``integrate_color`` on the grid of ``box`` and ``dims`` at
+    ``points [n,3]`` (``tn_tsdf_sample_colors``) -- the trilinear interpolants of ``sum w rgb`` and of ``sum w`` in the point's cell
+    (a point outside the box is clamped onto it), divided; nodes without colour carry no weight and drop out of the average.
+    ``den == 0`` (then ``rgb == 0``): no coloured node around the point, or a coordinate that is not finite."""
+    lo, h, dims = cut_box(box, dims, "tsdf")
+    if points.dim() != 2 or points.size(1) != 3 or points.dtype != torch.float32:
+        raise ValueError("tsdf.sample_colors: points must be [n,3] float32")
+    if C.dtype != torch.float32 or tuple(C.shape) != (dims[2] + 1, dims[1] + 1, dims[0] + 1, 4):
+        raise ValueError("tsdf.sample_colors: C must be a float32 tensor [nz+1, ny+1, nx+1, 4]")
+    from ctypes import c_int64                                     # (the module's alias C is the volume here)
+    dev = L.require_cuda(C, points)
+    n = points.size(0)
+    out = torch.zeros((n, 4), dtype=torch.float32, device=dev)     # (zeros: an axis of 0 cells launches nothing)
+    lo_c, h_c, dims_c = _grid(lo, h, dims)
+    if n:
+        L.call("tn_tsdf_sample_colors", dev, L.ptr(C), dims_c, lo_c, h_c, L.ptr(points), c_int64(n), L.ptr(out))
+    return out[:, :3].contiguous(), out[:, 3].contiguous()
 
 
 def field(S: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
@@ -117,22 +179,31 @@ def export_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: 
     truncation ``trunc`` (``None``: ``4 max(h)``), the zero level extracted (``mesh.extract``), the faces of unobserved cells masked,
     and ``mesh.filter_components(max(1, min_faces), keep_fraction)`` -- which drops the masked faces and orphaned vertices, and the
     pieces below the threshold.  Returns ``(vertices, normals, colors, faces)`` on the device as ``mesh.export_mesh`` does -- colours
-    from ``mesh.vertex_colors``, zeros when switched off -- and writes ``path`` (``mesh.write_mesh_ply``) when one is given."""
+    from ``mesh.vertex_colors``, zeros when switched off -- and writes ``path`` (``mesh.write_mesh_ply``) when one is given.
+    ``colors="fused"``: the colours come from the renders instead of the decoder -- the render loop also keeps every
+    view's ``rgb`` (12 B per pixel beside the 8 B of depth and opacity it keeps anyway), ``integrate_color`` fuses them into a colour
+    volume with the renderer's background taken out, and the surviving vertices take ``mesh.color_bytes(sample_colors(...))``; a
+    vertex no coloured node surrounds (``den == 0``) takes the decoder's colour.  Any other string is a ``ValueError``."""
     from . import mesh as M
     from .points import DEPTH_KEYS
     M._one_rank("export_tsdf_mesh", trainer)
     M.component_threshold(min_faces, keep_fraction, 0)             # the arguments, before any device work
     if depth not in DEPTH_KEYS:
         raise ValueError(f"export_tsdf_mesh: depth must be one of {sorted(DEPTH_KEYS)}, not {depth!r}")
+    if isinstance(colors, str) and colors != "fused":
+        raise ValueError(f"export_tsdf_mesh: colors must be True, False or 'fused', not {colors!r}")
+    fused = isinstance(colors, str)
     box, lo, h, dims, trunc = M._export_grid("export_tsdf_mesh", trainer, crop, resolution, trunc, lambda h: 4.0 * float(np.max(h)), "trunc")
     idx = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
     dev = trainer.device
     S = torch.zeros((dims[2] + 1, dims[1] + 1, dims[0] + 1), dtype=torch.float32, device=dev)
     W = torch.zeros_like(S)
+    volume = torch.zeros(S.shape + (4,), dtype=torch.float32, device=dev) if fused else None
     if idx:
         cams = camera_table(dataset, idx, dev)
         dist = torch.empty(cams.n_rays, dtype=torch.float32, device=dev)
         opacity = torch.empty(cams.n_rays, dtype=torch.float32, device=dev)
+        rgb = torch.empty((cams.n_rays, 3), dtype=torch.float32, device=dev) if fused else None
         for k, i in enumerate(idx):
             item = dataset[i]
             o, d = item["rays_o"].reshape(-1, 3).to(dev), item["rays_d"].reshape(-1, 3).to(dev)
@@ -141,8 +212,21 @@ def export_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: 
             maps = trainer.render_rays(o, d, maps=True)
             dist[cams.offsets[k]:cams.offsets[k + 1]] = maps[DEPTH_KEYS[depth]].reshape(-1)
             opacity[cams.offsets[k]:cams.offsets[k + 1]] = maps["opacity"].reshape(-1)
+            if fused:
+                rgb[cams.offsets[k]:cams.offsets[k + 1]] = maps["rgb"].reshape(-1, 3)
         integrate(cams, dist, opacity, box, dims, trunc, state=(S, W))          # (box and dims give lo and h again: cut_box both times)
+        if fused:
+            integrate_color(cams, dist, opacity, rgb, trainer.renderer._bg(dev), box, dims, trunc, state=volume)
     vertices, normals, faces, cells = M.extract_with_cells(field(S, W), lo, h, 0.0)
     faces = mask_faces(W, dims, cells, vertices.size(0), faces)
     vertices, normals, _, faces = M.filter_components(vertices, normals, None, faces, min_faces=max(1, int(min_faces)), keep_fraction=keep_fraction)
-    return M._finish_export(trainer, path, vertices, normals, faces, colors)
+    if not fused:
+        return M._finish_export(trainer, path, vertices, normals, faces, colors)
+    sampled, den = sample_colors(volume, box, dims, vertices)
+    out = M.color_bytes(sampled)
+    bare = (den == 0).nonzero().reshape(-1)                        # no coloured node around the vertex: ask the decoder, for these alone
+    if bare.numel():
+        out[bare] = M.vertex_colors(trainer, vertices[bare].contiguous(), normals[bare].contiguous())
+    if path is not None:
+        M.write_mesh_ply(path, vertices, normals, out, faces)
+    return vertices, normals, out, faces

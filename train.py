@@ -14,7 +14,7 @@ from pathlib import Path
 
 # (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight, --ssim,
 # --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop, --normals, --export_mesh, --mesh_level, --mesh_crop, --mesh_min_faces, --mesh_keep_fraction,
-# --export_tsdf_mesh and --tsdf_trunc
+# --export_tsdf_mesh, --tsdf_trunc and --tsdf_colors
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -48,6 +48,8 @@ FLAGS = (
                                                                         "field, its zero level as a triangle mesh, R cells on the longest axis of the box (0: off); "
                                                                         "--mesh_crop, --mesh_min_faces and --mesh_keep_fraction apply to it too")),
     ("--tsdf_trunc", dict(type=float, default=None, metavar="T", help="with --export_tsdf_mesh: the truncation distance (default: 4 cells)")),
+    ("--tsdf_colors", dict(type=str, default="decoder", choices=["decoder", "fused"],
+                           help="with --export_tsdf_mesh: vertex colours from the colour decoder at the vertex, or fused from the test views' renders")),
 )
 
 
@@ -64,6 +66,8 @@ def parse_args(argv=None):
         parser.error("--mesh_min_faces must be >= 0 and --mesh_keep_fraction lie in [0, 1]")
     if args.tsdf_trunc is not None and not args.export_tsdf_mesh:
         parser.error("--tsdf_trunc is the truncation of --export_tsdf_mesh R: give that too")
+    if args.tsdf_colors == "fused" and not args.export_tsdf_mesh:
+        parser.error("--tsdf_colors fused colours the mesh of --export_tsdf_mesh R: give that too")
     if args.export_tsdf_mesh < 0 or (args.tsdf_trunc is not None and not 0.0 < args.tsdf_trunc < float("inf")):
         parser.error("--export_tsdf_mesh must be >= 0 and --tsdf_trunc finite and > 0")
     return args
@@ -124,7 +128,8 @@ def main(argv=None):
     train(cfg, train_rays, eval_set, test_set, run_dir, args.eval_every, args.eval_n, args.max_steps, render_maps=args.render_maps, ssim=args.ssim,
           pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop, normals=args.normals,
           mesh=args.export_mesh, mesh_level=args.mesh_level, mesh_crop=args.mesh_crop, mesh_min_faces=args.mesh_min_faces,
-          mesh_keep_fraction=args.mesh_keep_fraction, tsdf_mesh=args.export_tsdf_mesh, tsdf_trunc=args.tsdf_trunc)
+          mesh_keep_fraction=args.mesh_keep_fraction, tsdf_mesh=args.export_tsdf_mesh, tsdf_trunc=args.tsdf_trunc,
+          tsdf_colors=args.tsdf_colors)
 
 
 if __name__ == "__main__":
