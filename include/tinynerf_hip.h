@@ -937,6 +937,73 @@ int tn_tsdf_sample_colors(const float *C,                                       
                           int64_t n,
                           float *out,                                           /* [n][4]: r, g, b, den */
                           void *stream);
+/* Taubin (lambda | mu) smoothing of an indexed triangle mesh, the deterministic vertex adjacency it runs on, and the vertex normals of
+ * the smoothed faces: all on the device; the adjacency in integers, passes and normals in fp32.
+ * Input.  V vertices and F faces, faces [F,3] int32, as tn_mesh_components takes them.  A face TAKES PART when its three indices lie in
+ *   [0, V) and are pairwise different -- so neither a (-1,-1,-1) row of tn_tsdf_mask_faces nor a face with a repeated index does; every
+ *   other face is ignored everywhere below.  F' = the participating faces.
+ * Adjacency.  Vertex v's ROW holds one pair (a, b) for every participating face that names v: the face's other two corners in its
+ *   cyclic order after v -- face (v,a,b), (b,v,a) or (a,b,v) all give (a,b) --, the pairs in ascending face id (a face names v at most
+ *   once).  d(v) is the row length.  offsets int32 [V+1] = the exclusive prefix sums of d, in pairs: offsets[V] = 3 F'.  pairs int32
+ *   [3F,2] holds the rows back to back; rows at or beyond offsets[V] are not written.  pinned uint8 [V] = 1 when d(v) == 0, or when some
+ *   id among the row's 2 d(v) entries does not occur exactly twice among them -- an edge at v with one incident face (a boundary) or
+ *   more than two (non-manifold) --, else 0.  stats int64 [3] = (F', the vertices with pinned == 0, the largest d).  The result is a
+ *   function of the input alone: the same bytes on every call, whatever the workspace held before.
+ * One smoothing pass with the factor f, in [V,3] -> out [V,3], out != in.  A vertex MOVES when d(v) > 0 and, with a pinned array,
+ *   pinned[v] == 0.  For one that moves: s = the fp32 sum of the 2 d(v) positions in[a], in[b] of its row in row order (a before b,
+ *   from 0), c = s / (2 d(v)) (one correctly rounded division), out[v] = fmaf(f, c - in[v], in[v]).  On a closed manifold mesh this is
+ *   the uniform umbrella operator with every neighbour counted twice.  A vertex that does not move has its row copied bit for bit.
+ *   Positions that are not finite are not special-cased: they propagate.
+ * Taubin smoothing, N iterations: N times a pass with f = lambda followed by a pass with f = mu (the usual 0.5 and -0.53: a low-pass
+ *   filter that does not shrink the shape as lambda alone does).  tn_mesh_smooth enqueues the 2 N passes itself -- lambda into
+ *   `scratch`, mu into `out`, so the result lands in `out` whatever N is -- and gives bit for bit what chaining tn_mesh_smooth_pass
+ *   gives; N == 0 copies `vertices` to `out` (no launch).
+ * Vertex normals of the faces.  g(v) = the sum over the row, in row order, of (p[a] - p[v]) x (p[b] - p[v]) -- twice the area-weighted
+ *   sum of the face normals; each component accumulated with two fmaf per pair.  Faces are counter-clockwise seen from outside
+ *   (tn_mesh_extract's are), so g points from dense to empty as the normals of tn_mesh_extract do.  n(v) = g / |g|,
+ *   |g| = sqrtf(fmaf(gx, gx, fmaf(gy, gy, gz gz))); where d(v) == 0 or |g| is 0 or not finite, n(v) is row v of `fallback` [V,3], or 0
+ *   without one.
+ * tn_mesh_adjacency: a memset and nine launches on `stream`, no host read-back and no loop driven from the host -- integer atomicAdd
+ *   of the participating corners into per-vertex degrees; per-workgroup sums and one workgroup scanning them (1024 workgroups a
+ *   trip); offsets; the corner ids 3 f + k filled through per-vertex cursors (integer atomicAdd chooses the slot) into the workspace;
+ *   one lane per slot ranking its corner id among its row's and storing the pair at that rank; one lane per slot counting its pair's
+ *   ids over the row and storing pinned = 1 where a count is not 2; per-workgroup partial stats; one workgroup reducing them in a fixed
+ *   order.  The atomics choose the route, not the result: integer sums do not depend on the order of their operands, and a row's
+ *   corner ids are distinct, so their ranks are the same permutation wherever the cursors put them.  No floating-point atomics.
+ *   The degree is unbounded and every degree is handled; ranking and counting read the row once per slot, so the work is QUADRATIC in
+ *   the degree (spread over the row's d lanes) -- a closed manifold Surface Nets mesh stays at or below 12, real ones reach 24 where two sheets touch.  `workspace`:
+ *   tn_mesh_adjacency_workspace_bytes; with G = ceil(V / 256) it is 24 G + 8 ceil(V / 2) + 8 ceil(3 F / 2) bytes, 8-byte aligned like
+ *   `stats`; contents undefined afterwards.
+ * tn_mesh_smooth_pass, tn_mesh_vertex_normals: one launch each, one lane per vertex, no atomics.
+ * Checked before any launch: TN_E_SIZE for a negative size, V or F >= 2^31, 3 F >= 2^31 (offsets are int32), iterations < 0;
+ *   TN_E_CONFIG for a factor / lambda / mu that is not finite, for `out` aliasing `in` (tn_mesh_smooth: vertices, scratch and out
+ *   pairwise); TN_E_NULL for a null required pointer (stats always; with V > 0 offsets, pinned and the workspace, faces and pairs with
+ *   F > 0; for the others everything but `pinned` / `fallback`, with V > 0); TN_E_ALIGN (8 bytes for workspace and stats, 4 for the
+ *   rest).  V == 0 writes stats of 0 and returns TN_OK without reading anything.  F == 0 pins every vertex: offsets all 0.
+ * No reference call site: the reference renders images and exports no geometry. */
+int tn_mesh_adjacency_workspace_bytes(int64_t n_vertices, int64_t n_faces, int64_t *bytes);    /* host only */
+int tn_mesh_adjacency(const int32_t *faces,                                     /* [n_faces,3] device */
+                      int64_t n_vertices, int64_t n_faces,
+                      int32_t *offsets,                                         /* [n_vertices+1] */
+                      int32_t *pairs,                                           /* [3 n_faces,2] */
+                      uint8_t *pinned,                                          /* [n_vertices] */
+                      int64_t *stats,                                           /* device, 3 values */
+                      void *workspace, void *stream);
+int tn_mesh_smooth_pass(const float *in,                                        /* [n_vertices,3] */
+                        const int32_t *offsets, const int32_t *pairs,           /* tn_mesh_adjacency's */
+                        const uint8_t *pinned,                                  /* [n_vertices] or NULL: every vertex with a row moves */
+                        int64_t n_vertices, float factor,
+                        float *out,                                             /* [n_vertices,3], not `in` */
+                        void *stream);
+int tn_mesh_smooth(const float *vertices, const int32_t *offsets, const int32_t *pairs, const uint8_t *pinned, int64_t n_vertices,
+                   int32_t iterations, float lambda, float mu,
+                   float *scratch,                                              /* [n_vertices,3] */
+                   float *out,                                                  /* [n_vertices,3] */
+                   void *stream);
+int tn_mesh_vertex_normals(const float *vertices, const int32_t *offsets, const int32_t *pairs, int64_t n_vertices,
+                           const float *fallback,                               /* [n_vertices,3] or NULL */
+                           float *normals,                                      /* [n_vertices,3] */
+                           void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * optimizer step of the harness                      (reference run.py:186,258-260: torch.optim.Adam)

@@ -52,6 +52,7 @@ SOURCES = {
     "mlp_b3_layers.hip": FAST + ["-munsafe-fp-atomics"],
     "mesh_components.hip": FAST,      # mesh.hip's flags; after the training kernels, so that the objects before it link where they did
     "tsdf.hip": FAST,                 # likewise
+    "mesh_smooth.hip": FAST,          # likewise
 }
 
 

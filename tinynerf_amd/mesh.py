@@ -5,6 +5,7 @@ crosses; an indexed mesh, closed and consistently oriented wherever the surface 
 * ``extract`` -- ``tn_mesh_extract`` over a tensor of node values: vertices, normals, faces; ``extract_with_cells`` -- and the cell -> vertex id map;
 * ``density_grid`` / ``extract_mesh`` -- the node values of a trainer / of any density callable, and their mesh;
 * ``export_mesh`` -- a trainer's mesh with vertex colours from its colour decoder, written to ``path``;
+* ``adjacency`` / ``smooth`` / ``vertex_normals`` / ``smooth_mesh`` -- Taubin smoothing of a mesh and the normals of its faces (DESIGN 6l);
 * ``write_mesh_ply`` / ``read_mesh_ply`` -- binary little-endian PLY, 27 B per vertex, 13 B per face.
 
 The mesh is in the frame the rays are in: for a capture that is the frame after ``data.orient_poses``, not the capture's own.
@@ -223,13 +224,21 @@ def _density_surface(trainer, lo, h, dims, sigma):
     return extract(values, lo, h, math.log(sigma))
 
 
-def _finish_export(trainer, path, vertices, normals, faces, colors):
-    """the end of every mesh export: colours from ``vertex_colors`` (zeros when switched off or without vertices), ``path`` written
-    (``write_mesh_ply``) when one is given -> ``(vertices, normals, colors, faces)``"""
-    rgb = vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=vertices.device)
+def _write_export(path, vertices, normals, rgb, faces, smooth, smooth_lambda, smooth_mu):
+    """the last step of every mesh export: ``smooth_mesh`` when ``smooth`` > 0 (the colours were taken at the extracted positions),
+    ``path`` written (``write_mesh_ply``) when one is given -> ``(vertices, normals, colors, faces)``"""
+    if smooth:
+        vertices, normals = smooth_mesh(vertices, normals, faces, smooth, lam=smooth_lambda, mu=smooth_mu)
     if path is not None:
         write_mesh_ply(path, vertices, normals, rgb, faces)
     return vertices, normals, rgb, faces
+
+
+def _finish_export(trainer, path, vertices, normals, faces, colors, smooth=0, smooth_lambda=0.5, smooth_mu=-0.53):
+    """the end of every mesh export: colours from ``vertex_colors`` (zeros when switched off or without vertices), then
+    ``_write_export`` -> ``(vertices, normals, colors, faces)``"""
+    rgb = vertex_colors(trainer, vertices, normals) if colors and vertices.size(0) else torch.zeros((vertices.size(0), 3), dtype=torch.uint8, device=vertices.device)
+    return _write_export(path, vertices, normals, rgb, faces, smooth, smooth_lambda, smooth_mu)
 
 
 @torch.no_grad()
@@ -327,10 +336,132 @@ def export_clean_mesh(trainer, path=None, resolution: int = 256, level: Optional
     component_threshold(min_faces, keep_fraction, 0)
     if not min_faces and not keep_fraction:
         return export_mesh(trainer, path, resolution=resolution, level=level, crop=crop, colors=colors)
-    _, lo, h, dims, sigma = _export_grid("export_clean_mesh", trainer, crop, resolution, level, default_level, "level is a density: it")
-    vertices, normals, faces = _density_surface(trainer, lo, h, dims, sigma)
-    vertices, normals, _, faces = filter_components(vertices, normals, None, faces, min_faces=min_faces, keep_fraction=keep_fraction)
+    vertices, normals, faces = _clean_surface("export_clean_mesh", trainer, resolution, level, crop, min_faces, keep_fraction)
     return _finish_export(trainer, path, vertices, normals, faces, colors)
+
+
+def _clean_surface(who, trainer, resolution, level, crop, min_faces, keep_fraction):
+    """``(vertices, normals, faces)``: the density's surface on the export grid, through ``filter_components`` when an option is not 0"""
+    _, lo, h, dims, sigma = _export_grid(who, trainer, crop, resolution, level, default_level, "level is a density: it")
+    vertices, normals, faces = _density_surface(trainer, lo, h, dims, sigma)
+    if min_faces or keep_fraction:
+        vertices, normals, _, faces = filter_components(vertices, normals, None, faces, min_faces=min_faces, keep_fraction=keep_fraction)
+    return vertices, normals, faces
+
+
+@torch.no_grad()
+def export_smooth_mesh(trainer, path=None, resolution: int = 256, level: Optional[float] = None, crop=None, colors: bool = True,
+                       min_faces: int = 0, keep_fraction: float = 0.0, smooth: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53):
+    """``export_clean_mesh`` with ``smooth_mesh(vertices, normals, faces, smooth, smooth_lambda, smooth_mu)`` as the last step before
+    the file: the order is extraction, component filter (when ``min_faces`` or ``keep_fraction`` is not 0), colours,
+    smoothing.  The colours are the decoder's at the EXTRACTED positions with the extracted normals; the tuple and the file carry the
+    smoothed positions and the normals of the smoothed faces.  With ``smooth == 0`` it IS a call of ``export_clean_mesh`` -- the same
+    bytes, nothing of the smoothing launched.  (``export_mesh`` and ``export_clean_mesh`` keep their signatures, so this is a
+    function beside them.)"""
+    _one_rank("export_smooth_mesh", trainer)
+    component_threshold(min_faces, keep_fraction, 0)
+    if not check_smooth("export_smooth_mesh", smooth, smooth_lambda, smooth_mu):
+        return export_clean_mesh(trainer, path, resolution=resolution, level=level, crop=crop, colors=colors, min_faces=min_faces, keep_fraction=keep_fraction)
+    vertices, normals, faces = _clean_surface("export_smooth_mesh", trainer, resolution, level, crop, min_faces, keep_fraction)
+    return _finish_export(trainer, path, vertices, normals, faces, colors, smooth, smooth_lambda, smooth_mu)
+
+
+def check_smooth(who, iterations, lam=0.5, mu=-0.53) -> int:
+    """``iterations`` as an int; ``ValueError`` in the name ``who`` for ``iterations < 0`` or not an integer, for a ``lam`` / ``mu`` that is not finite"""
+    if isinstance(iterations, bool) or int(iterations) != iterations or int(iterations) < 0:
+        raise ValueError(f"{who}: the smoothing iterations must be an integer >= 0")
+    if not (math.isfinite(float(lam)) and math.isfinite(float(mu))):
+        raise ValueError(f"{who}: the smoothing factors lambda and mu must be finite")
+    return int(iterations)
+
+
+def _check_mesh(who, vertices, faces, **rows):
+    """shapes and dtypes of a mesh: ``vertices [V,3] float32``, ``faces [F,3] int32``, every given ``rows`` tensor ``[V,3] float32``"""
+    if vertices.dim() != 2 or vertices.size(1) != 3 or vertices.dtype != torch.float32:
+        raise ValueError(f"{who}: vertices must be [V,3] float32")
+    if faces.dim() != 2 or faces.size(1) != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{who}: faces must be [F,3] int32")
+    for name, t in rows.items():
+        if t is not None and (t.shape != vertices.shape or t.dtype != torch.float32):
+            raise ValueError(f"{who}: {name} must be [V,3] float32")
+
+
+def adjacency(faces: torch.Tensor, n_vertices: int):
+    """``(offsets [V+1] int32, pairs [3F,2] int32, pinned [V] uint8, stats)`` of the mesh ``faces [F,3] int32`` over ``n_vertices``
+    vertices (``tn_mesh_adjacency``): vertex ``v``'s row ``pairs[offsets[v]:offsets[v+1]]`` holds the other two corners
+    ``(a, b)`` of every face that names ``v``, in the face's cyclic order, the faces ascending; ``pinned[v]`` is 1 for a vertex
+    without faces, on an open boundary or on a non-manifold edge; ``stats = (participating faces, free vertices, largest degree)`` as
+    ints, from one read-back.  A face with an index outside ``[0, n_vertices)`` or a repeated index takes no part; rows of ``pairs``
+    from ``offsets[V]`` on are not written.  The same bytes on every call."""
+    V = int(n_vertices)
+    if faces.dim() != 2 or faces.size(1) != 3 or faces.dtype != torch.int32 or V < 0:
+        raise ValueError("adjacency: faces must be [F,3] int32 and n_vertices >= 0")
+    dev = L.require_cuda(faces)
+    F = faces.size(0)
+    nbytes = C.c_int64(0)
+    L.call_plain("tn_mesh_adjacency_workspace_bytes", C.c_int64(V), C.c_int64(F), C.byref(nbytes))
+    workspace = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+    offsets = torch.zeros(V + 1, dtype=torch.int32, device=dev)    # (zeros: V == 0 launches nothing)
+    pairs = torch.empty((max(3 * F, 1), 2), dtype=torch.int32, device=dev)[:3 * F]      # (a pointer even without faces)
+    pinned = torch.empty(V, dtype=torch.uint8, device=dev)
+    stats = torch.empty(3, dtype=torch.int64, device=dev)
+    L.call("tn_mesh_adjacency", dev, L.ptr(faces) if F else None, C.c_int64(V), C.c_int64(F), L.ptr(offsets), L.ptr(pairs), L.ptr(pinned) if V else None,
+           L.ptr(stats), L.ptr(workspace) if V else None)
+    return offsets, pairs, pinned, tuple(stats.tolist())
+
+
+def _adjacency_of(who, faces, V, adjacency_):
+    offsets, pairs, pinned = adjacency(faces, V)[:3] if adjacency_ is None else tuple(adjacency_)[:3]
+    if offsets.dtype != torch.int32 or offsets.numel() != V + 1 or pairs.dtype != torch.int32 or pinned.dtype != torch.uint8 or pinned.numel() != V:
+        raise ValueError(f"{who}: adjacency must be mesh.adjacency's (offsets [V+1] int32, pairs [.,2] int32, pinned [V] uint8, ...)")
+    return offsets, pairs, pinned
+
+
+def smooth(vertices: torch.Tensor, faces: torch.Tensor, iterations: int, lam: float = 0.5, mu: float = -0.53, pin_boundary: bool = True,
+           adjacency=None) -> torch.Tensor:
+    """``vertices [V,3] float32`` after ``iterations`` Taubin iterations over the mesh ``faces`` (``tn_mesh_smooth``): each
+    a pass ``p += lam (c - p)`` and a pass ``p += mu (c - p)``, ``c`` the mean of the vertex's row of ``adjacency`` -- the uniform
+    umbrella operator; with ``mu < -lam < 0`` a low-pass filter that does not shrink the shape.  ``pin_boundary``: vertices on an open
+    boundary or a non-manifold edge stay where they are (``pinned``); without it every vertex with a face moves.  ``adjacency``: what
+    ``adjacency(faces, V)`` returned, to build it once for several calls.  ``iterations == 0`` returns ``vertices`` itself."""
+    n = check_smooth("smooth", iterations, lam, mu)
+    _check_mesh("smooth", vertices, faces)
+    if n == 0:
+        return vertices
+    dev = L.require_cuda(vertices, faces)
+    V = vertices.size(0)
+    offsets, pairs, pinned = _adjacency_of("smooth", faces, V, adjacency)
+    scratch, out = torch.empty_like(vertices), torch.empty_like(vertices)
+    if V:
+        L.call("tn_mesh_smooth", dev, L.ptr(vertices), L.ptr(offsets), L.ptr(pairs), L.ptr(pinned) if pin_boundary else None, C.c_int64(V),
+               C.c_int32(n), C.c_float(lam), C.c_float(mu), L.ptr(scratch), L.ptr(out))
+    return out
+
+
+def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor, fallback: Optional[torch.Tensor] = None, adjacency=None) -> torch.Tensor:
+    """``[V,3] float32``: the unit normals of the mesh's vertices from its faces (``tn_mesh_vertex_normals``) -- the
+    area-weighted sum of the normals of the faces around the vertex, normalised; faces counter-clockwise seen from outside give
+    normals that point outside, as ``extract``'s do.  A vertex without faces or with a sum of length 0 or not finite takes its row of
+    ``fallback``, or 0 without one."""
+    _check_mesh("vertex_normals", vertices, faces, fallback=fallback)
+    dev = L.require_cuda(vertices, faces, fallback)
+    V = vertices.size(0)
+    offsets, pairs, _ = _adjacency_of("vertex_normals", faces, V, adjacency)
+    out = torch.empty_like(vertices)
+    if V:
+        L.call("tn_mesh_vertex_normals", dev, L.ptr(vertices), L.ptr(offsets), L.ptr(pairs), C.c_int64(V), L.ptr(fallback), L.ptr(out))
+    return out
+
+
+def smooth_mesh(vertices: torch.Tensor, normals: Optional[torch.Tensor], faces: torch.Tensor, iterations: int, lam: float = 0.5, mu: float = -0.53,
+                pin_boundary: bool = True):
+    """``(vertices, normals)``: ``smooth`` and then ``vertex_normals`` of the smoothed faces with the old ``normals`` as the fallback,
+    over one ``adjacency``.  ``iterations == 0`` still recomputes the normals from the faces."""
+    check_smooth("smooth_mesh", iterations, lam, mu)
+    _check_mesh("smooth_mesh", vertices, faces, normals=normals)
+    adj = adjacency(faces, vertices.size(0))
+    moved = smooth(vertices, faces, iterations, lam=lam, mu=mu, pin_boundary=pin_boundary, adjacency=adj)
+    return moved, vertex_normals(moved, faces, fallback=normals, adjacency=adj)
 
 
 def _host(x, dtype) -> np.ndarray:

@@ -938,7 +938,7 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
           eval_n: int = 1, max_steps: Optional[int] = None, device: Optional[torch.device] = None, log_every: int = 100,
           render_maps: bool = False, ssim: bool = False, pointcloud: int = 0, pointcloud_crop=None,
           mesh: int = 0, mesh_level: Optional[float] = None, mesh_crop=None, mesh_min_faces: int = 0, mesh_keep_fraction: float = 0.0,
-          tsdf_mesh: int = 0, tsdf_trunc: Optional[float] = None, tsdf_colors: str = "decoder", normals: bool = False):
+          tsdf_mesh: int = 0, tsdf_trunc: Optional[float] = None, tsdf_colors: str = "decoder", mesh_smooth: int = 0, normals: bool = False):
     """The reference's train() on the HIP path.  `train_rays` is a data.RaysDataset on the device, or a data.CameraRaysDataset (a
     photographed scene: the trainer makes its rays from the camera table, ``Trainer(ray_source=...)``).  ``render_maps``: the final
     test render also writes the depth / opacity maps of every image (``infer(maps=True)``).  ``ssim``: the periodic evaluation and
@@ -958,8 +958,13 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
     ``tsdf_trunc``: its ``trunc``; ``mesh_crop``, ``mesh_min_faces`` and ``mesh_keep_fraction`` apply to it as well).  At 0 nothing of
     it is imported, allocated or launched.  ``tsdf_colors``: ``"decoder"`` -- the colour decoder asked at every vertex, the file what
     it always was -- or ``"fused"`` -- the test views' rendered colours fused into a colour volume beside the TSDF and sampled at the
-    vertices; ``ValueError`` for anything else, before the first step."""
+    vertices; ``ValueError`` for anything else, before the first step.  ``mesh_smooth`` > 0: ``mesh.ply`` and
+    ``tsdf_mesh.ply`` are smoothed by that many Taubin iterations as the last step before they are written, their normals recomputed
+    from the smoothed faces (``mesh.export_smooth_mesh`` / ``tsdf.export_smooth_tsdf_mesh``); ``ValueError`` for a negative count, before the first step.  At 0
+    the exporters are called exactly as before and the files are byte for byte what they were."""
     import json
+    if isinstance(mesh_smooth, bool) or int(mesh_smooth) != mesh_smooth or mesh_smooth < 0:
+        raise ValueError(f"train(mesh_smooth=...): an integer >= 0, not {mesh_smooth!r}")
     if tsdf_colors not in ("decoder", "fused"):
         raise ValueError(f"train(tsdf_colors=...): 'decoder' or 'fused', not {tsdf_colors!r}")
     if normals and cfg.method not in ("kplanes", "hashgrid"):
@@ -1001,7 +1006,11 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
                 tr, test_set, idx, output / "pointcloud.ply", n_points=pointcloud, crop=pointcloud_crop, seed=cfg.seed,
                 rendered=rendered if render_maps else None)
         if mesh > 0 and output is not None:
-            if mesh_min_faces or mesh_keep_fraction:
+            if mesh_smooth:
+                from .mesh import export_smooth_mesh
+                export_smooth_mesh(tr, output / "mesh.ply", resolution=mesh, level=mesh_level, crop=mesh_crop, min_faces=mesh_min_faces,
+                                   keep_fraction=mesh_keep_fraction, smooth=int(mesh_smooth))
+            elif mesh_min_faces or mesh_keep_fraction:
                 from .mesh import export_clean_mesh
                 export_clean_mesh(tr, output / "mesh.ply", resolution=mesh, level=mesh_level, crop=mesh_crop, min_faces=mesh_min_faces,
                                   keep_fraction=mesh_keep_fraction)
@@ -1009,9 +1018,11 @@ def train(cfg: TrainConfig, train_rays, eval_set=None, test_set=None, output=Non
                 from .mesh import export_mesh
                 export_mesh(tr, output / "mesh.ply", resolution=mesh, level=mesh_level, crop=mesh_crop)
         if tsdf_mesh > 0 and output is not None:
-            from .tsdf import export_tsdf_mesh
-            export_tsdf_mesh(tr, test_set, output / "tsdf_mesh.ply", resolution=tsdf_mesh, trunc=tsdf_trunc, crop=mesh_crop,
-                             min_faces=mesh_min_faces, keep_fraction=mesh_keep_fraction, colors="fused" if tsdf_colors == "fused" else True)
+            from .tsdf import export_smooth_tsdf_mesh, export_tsdf_mesh
+            more = {"smooth": int(mesh_smooth)} if mesh_smooth else {}
+            (export_smooth_tsdf_mesh if mesh_smooth else export_tsdf_mesh)(
+                tr, test_set, output / "tsdf_mesh.ply", resolution=tsdf_mesh, trunc=tsdf_trunc, crop=mesh_crop,
+                min_faces=mesh_min_faces, keep_fraction=mesh_keep_fraction, colors="fused" if tsdf_colors == "fused" else True, **more)
         if render_maps:
             rendered = [r["rgb"] for r in rendered]
         if test_set.rgbs:

@@ -9,7 +9,8 @@ over the whole ray, so fog averages out, and views that disagree vote.
 * ``field`` -- the mesh field ``-S / W`` (``-1`` where ``W == 0``), level 0, inside ``>= 0``;
 * ``mask_faces`` -- ``tn_tsdf_mask_faces``: faces of cells with an unobserved corner become ``(-1, -1, -1)``;
 * ``camera_table`` -- the pose-only ``rays.CameraRays`` of a ``PoseDataset`` / ``CameraPoseDataset``;
-* ``export_tsdf_mesh`` -- render, integrate, extract, mask, filter, colour (the decoder's, or ``"fused"`` from the renders), write.
+* ``export_tsdf_mesh`` -- render, integrate, extract, mask, filter, colour (the decoder's, or ``"fused"`` from the renders), write;
+* ``export_smooth_tsdf_mesh`` -- the same with ``mesh.smooth_mesh`` as the last step before the file.
 
 torch is plumbing only; there is no CPU path.  No reference counterpart: the reference renders images and exports no geometry.
 """
@@ -184,16 +185,35 @@ def export_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: 
     view's ``rgb`` (12 B per pixel beside the 8 B of depth and opacity it keeps anyway), ``integrate_color`` fuses them into a colour
     volume with the renderer's background taken out, and the surviving vertices take ``mesh.color_bytes(sample_colors(...))``; a
     vertex no coloured node surrounds (``den == 0``) takes the decoder's colour.  Any other string is a ``ValueError``."""
+    return _export_tsdf_mesh("export_tsdf_mesh", trainer, dataset, path, resolution, trunc, crop, indices, min_faces, keep_fraction, depth, colors, 0, 0.5, -0.53)
+
+
+@torch.no_grad()
+def export_smooth_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: Optional[float] = None, crop=None,
+                            indices: Optional[Sequence[int]] = None, min_faces: int = 0, keep_fraction: float = 0.0, depth: str = "expected",
+                            colors: bool = True, smooth: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53):
+    """``export_tsdf_mesh`` with ``mesh.smooth_mesh(vertices, normals, faces, smooth, smooth_lambda, smooth_mu)`` as the last step
+    before the file -- after the mask, the filter and the colours, which are asked or sampled at the EXTRACTED positions
+    with the extracted normals (the decoder's, the fused volume's and the fallback for bare vertices alike).  With ``smooth == 0``
+    it returns and writes what ``export_tsdf_mesh`` does and launches nothing of the smoothing.  (``export_tsdf_mesh`` keeps its
+    signature, so this is a function beside it.)"""
+    from . import mesh as M
+    smooth = M.check_smooth("export_smooth_tsdf_mesh", smooth, smooth_lambda, smooth_mu)
+    return _export_tsdf_mesh("export_smooth_tsdf_mesh", trainer, dataset, path, resolution, trunc, crop, indices, min_faces, keep_fraction, depth, colors,
+                             smooth, smooth_lambda, smooth_mu)
+
+
+def _export_tsdf_mesh(who, trainer, dataset, path, resolution, trunc, crop, indices, min_faces, keep_fraction, depth, colors, smooth, smooth_lambda, smooth_mu):
     from . import mesh as M
     from .points import DEPTH_KEYS
-    M._one_rank("export_tsdf_mesh", trainer)
+    M._one_rank(who, trainer)
     M.component_threshold(min_faces, keep_fraction, 0)             # the arguments, before any device work
     if depth not in DEPTH_KEYS:
-        raise ValueError(f"export_tsdf_mesh: depth must be one of {sorted(DEPTH_KEYS)}, not {depth!r}")
+        raise ValueError(f"{who}: depth must be one of {sorted(DEPTH_KEYS)}, not {depth!r}")
     if isinstance(colors, str) and colors != "fused":
-        raise ValueError(f"export_tsdf_mesh: colors must be True, False or 'fused', not {colors!r}")
+        raise ValueError(f"{who}: colors must be True, False or 'fused', not {colors!r}")
     fused = isinstance(colors, str)
-    box, lo, h, dims, trunc = M._export_grid("export_tsdf_mesh", trainer, crop, resolution, trunc, lambda h: 4.0 * float(np.max(h)), "trunc")
+    box, lo, h, dims, trunc = M._export_grid(who, trainer, crop, resolution, trunc, lambda h: 4.0 * float(np.max(h)), "trunc")
     idx = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
     dev = trainer.device
     S = torch.zeros((dims[2] + 1, dims[1] + 1, dims[0] + 1), dtype=torch.float32, device=dev)
@@ -208,7 +228,7 @@ def export_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: 
             item = dataset[i]
             o, d = item["rays_o"].reshape(-1, 3).to(dev), item["rays_d"].reshape(-1, 3).to(dev)
             if o.size(0) != cams.offsets[k + 1] - cams.offsets[k]:
-                raise RuntimeError("export_tsdf_mesh: a view's rays do not match the size its camera states")
+                raise RuntimeError(f"{who}: a view's rays do not match the size its camera states")
             maps = trainer.render_rays(o, d, maps=True)
             dist[cams.offsets[k]:cams.offsets[k + 1]] = maps[DEPTH_KEYS[depth]].reshape(-1)
             opacity[cams.offsets[k]:cams.offsets[k + 1]] = maps["opacity"].reshape(-1)
@@ -221,12 +241,10 @@ def export_tsdf_mesh(trainer, dataset, path=None, resolution: int = 256, trunc: 
     faces = mask_faces(W, dims, cells, vertices.size(0), faces)
     vertices, normals, _, faces = M.filter_components(vertices, normals, None, faces, min_faces=max(1, int(min_faces)), keep_fraction=keep_fraction)
     if not fused:
-        return M._finish_export(trainer, path, vertices, normals, faces, colors)
+        return M._finish_export(trainer, path, vertices, normals, faces, colors, smooth, smooth_lambda, smooth_mu)
     sampled, den = sample_colors(volume, box, dims, vertices)
     out = M.color_bytes(sampled)
     bare = (den == 0).nonzero().reshape(-1)                        # no coloured node around the vertex: ask the decoder, for these alone
     if bare.numel():
         out[bare] = M.vertex_colors(trainer, vertices[bare].contiguous(), normals[bare].contiguous())
-    if path is not None:
-        M.write_mesh_ply(path, vertices, normals, out, faces)
-    return vertices, normals, out, faces
+    return M._write_export(path, vertices, normals, out, faces, smooth, smooth_lambda, smooth_mu)

@@ -14,7 +14,7 @@ from pathlib import Path
 
 # (flag, keyword arguments) -- same names, defaults and choices as the reference's parser, plus --max_steps, --render_maps, --distortion_weight, --ssim,
 # --downscale, --holdout_every, --export_pointcloud, --pointcloud_crop, --normals, --export_mesh, --mesh_level, --mesh_crop, --mesh_min_faces, --mesh_keep_fraction,
-# --export_tsdf_mesh, --tsdf_trunc and --tsdf_colors
+# --export_tsdf_mesh, --tsdf_trunc, --tsdf_colors and --mesh_smooth
 FLAGS = (
     ("--data", dict(type=str, required=True, help="path to the data folder")),
     ("--datatype", dict(type=str, required=True, choices=["synthetic", "nerfstudio"])),
@@ -50,6 +50,8 @@ FLAGS = (
     ("--tsdf_trunc", dict(type=float, default=None, metavar="T", help="with --export_tsdf_mesh: the truncation distance (default: 4 cells)")),
     ("--tsdf_colors", dict(type=str, default="decoder", choices=["decoder", "fused"],
                            help="with --export_tsdf_mesh: vertex colours from the colour decoder at the vertex, or fused from the test views' renders")),
+    ("--mesh_smooth", dict(type=int, default=0, metavar="N", help="with --export_mesh / --export_tsdf_mesh: N Taubin smoothing iterations over the mesh before it is "
+                                                                  "written, its normals recomputed from the smoothed faces (0: off)")),
 )
 
 
@@ -70,6 +72,10 @@ def parse_args(argv=None):
         parser.error("--tsdf_colors fused colours the mesh of --export_tsdf_mesh R: give that too")
     if args.export_tsdf_mesh < 0 or (args.tsdf_trunc is not None and not 0.0 < args.tsdf_trunc < float("inf")):
         parser.error("--export_tsdf_mesh must be >= 0 and --tsdf_trunc finite and > 0")
+    if args.mesh_smooth < 0:
+        parser.error("--mesh_smooth must be >= 0")
+    if args.mesh_smooth and not (args.export_mesh or args.export_tsdf_mesh):
+        parser.error("--mesh_smooth smooths the mesh of --export_mesh R or --export_tsdf_mesh R: give one of them too")
     return args
 
 
@@ -129,7 +135,7 @@ def main(argv=None):
           pointcloud=args.export_pointcloud, pointcloud_crop=args.pointcloud_crop, normals=args.normals,
           mesh=args.export_mesh, mesh_level=args.mesh_level, mesh_crop=args.mesh_crop, mesh_min_faces=args.mesh_min_faces,
           mesh_keep_fraction=args.mesh_keep_fraction, tsdf_mesh=args.export_tsdf_mesh, tsdf_trunc=args.tsdf_trunc,
-          tsdf_colors=args.tsdf_colors)
+          tsdf_colors=args.tsdf_colors, mesh_smooth=args.mesh_smooth)
 
 
 if __name__ == "__main__":
