@@ -204,9 +204,9 @@ WS = 1 << 40                      # workspace bytes: large enough for every n be
 
 
 def call(lib, entry, shape="kplanes_colour_aux", partner="kplanes_sigma", flags=STASHED, pflags=STASHED, n=1000, kd=None,
-         coord_stride=7, x=PTR, ws=PTR, y=PTR, py=PTR, gx=PTR, gw=None, pgw=None, **kw):
+         coord_stride=7, x=PTR, ws=PTR, y=PTR, py=PTR, gx=PTR, gw=None, pgw=None, feat=PTR, pkw=None, **kw):
     d = head_desc(shape, flags, **kw) if shape else None
-    p = head_desc(partner, pflags) if partner else None
+    p = head_desc(partner, pflags, **(pkw or {})) if partner else None
     k = kd if kd is not None else kdesc()
     gw, pgw = gw or grads(5), pgw or grads(2)
     gp = ((C.c_void_p * 3) * 4)()
@@ -220,7 +220,7 @@ def call(lib, entry, shape="kplanes_colour_aux", partner="kplanes_sigma", flags=
     if entry == "tn_kplanes_mlp_fwd":
         return lib.tn_kplanes_mlp_fwd(K, x, C.c_int64(coord_stride), D, n, PTR, y, None)
     if entry == "tn_kplanes_mlp_fwd_pair":
-        return lib.tn_kplanes_mlp_fwd_pair(K, x, C.c_int64(coord_stride), D, P, PTR, n, PTR, y, py, ws, C.c_int64(WS), ws, C.c_int64(WS), None)
+        return lib.tn_kplanes_mlp_fwd_pair(K, x, C.c_int64(coord_stride), D, P, PTR, n, feat, y, py, ws, C.c_int64(WS), ws, C.c_int64(WS), None)
     if entry == "tn_mlp_bwd":
         return lib.tn_mlp_bwd(D, x, PTR, PTR, n, gw, gw, gx, ws, C.c_int64(WS), None)
     if entry == "tn_mlp_bwd_pair":
@@ -277,6 +277,13 @@ REFUSALS = [
     ("tn_kplanes_mlp_fwd_pair", E_ALIGN, dict(y=PTR + 4)),
     ("tn_kplanes_mlp_fwd_pair", E_CONFIG, dict(shape="kplanes_colour_dir")),
     ("tn_kplanes_mlp_fwd_pair", E_CONFIG, dict(flags=LEAN, pflags=LEAN)),
+    # the inference pair form (both workspaces NULL): the dummy operand line lies in the coordinates when there are no feature rows
+    ("tn_kplanes_mlp_fwd_pair", E_ALIGN, dict(ws=None, x=PTR + 4)),
+    ("tn_kplanes_mlp_fwd_pair", E_ALIGN, dict(ws=None, x=PTR + 4, feat=None)),
+    ("tn_kplanes_mlp_fwd_pair", E_SIZE, dict(ws=None, feat=None, n=1, coord_stride=3)),
+    ("tn_kplanes_mlp_fwd_pair", E_CONFIG, dict(ws=None, row_gate=PTR)),
+    ("tn_kplanes_mlp_fwd_pair", E_CONFIG, dict(ws=None, pkw=dict(row_gate=PTR))),
+    ("tn_kplanes_mlp_fwd_pair", E_CONFIG, dict(ws=None, feat=None, row_gate=PTR)),
     ("tn_mlp_bwd", E_NULL, dict(shape=None)),
     ("tn_mlp_bwd", E_CONFIG, dict(shape=(ENC_AUX_CAT, 96, 8, [147, 64, 64, 64, 3], 56))),
     ("tn_mlp_bwd", E_NULL, dict(ws=None)),
